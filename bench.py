@@ -10,8 +10,13 @@ per-GPU work is fixed (weak scaling); `value` = rows of all ranks / max-over-ran
 
 Output: ONE JSON line (rank 0).  `roofline.achieved` = algorithmic bytes of the suite (the distinct
 buffers it must read) / the average duration of the scan launch measured with HIP
-events on the engine's stream over the timed region; `cpu_baseline` = the C restatement of Spark
-2.2 deequ semantics (oracle/oracle.c, "port") timed on this host's cores on a bounded sample.
+events on the engine's stream over the timed region.
+
+A plain run sets up, warms up, times `--steps` steps and prints the line.  `--dump-outputs DIR`
+also writes the row the last timed step returned to DIR/row.npy (float64).  `--full` adds the
+measurements that take runs of their own (N=1 only): `h2d_inclusive` (the host-fed scan),
+`cpu_baseline` = the C restatement of Spark 2.2 deequ semantics (oracle/oracle.c, "port") timed on
+this host's cores on a bounded sample, and `workloads` (BASELINE.json configs[2]-[4]).
 """
 from __future__ import annotations
 
@@ -144,16 +149,26 @@ def main():
     ap.add_argument("--rows", type=int, default=1_000_000_000, help="rows per GPU")
     ap.add_argument("--batch-rows", type=int, default=1 << 26)
     ap.add_argument("--seed", type=int, default=7)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the row the last timed step returned "
+                         "(rank 0's, after the exchange with N > 1) to DIR/row.npy as float64")
+    ap.add_argument("--full", action="store_true",
+                    help="after the S10 leg (N=1 only) also run the host-fed measurement, the CPU "
+                         "baseline and the other workloads; the options below select among them")
     ap.add_argument("--cpu-rows", type=int, default=20_000_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-h2d", action="store_true", help="skip the host-fed (PCIe) measurement")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-h2d", action="store_true",
+                    help="with --full: skip the host-fed (PCIe) measurement")
     ap.add_argument("--workloads", default="c3,c4,c5",
-                    help="after the S10 leg (N=1 only): configs[2] (c3), configs[3] (c4) and "
-                         "configs[4] (c5) timed at their stated sizes; '' skips them")
+                    help="with --full: configs[2] (c3), configs[3] (c4) and configs[4] (c5) timed "
+                         "at their stated sizes; '' skips them")
     ap.add_argument("--workload-budget-s", type=float, default=360.0,
                     help="wall-clock budget of the whole run: a workload is skipped (and says so) "
                          "once it would start past this many seconds")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     t_start = time.perf_counter()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -238,6 +253,8 @@ def main():
     assert row[0] == args.rows * world or world > 1 or row[0] == args.rows
 
     traffic, traffic_src = load_traffic(args.rows, b_alg)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, row)
     if rank == 0:
         out = {
             "metric": METRIC,
@@ -277,17 +294,33 @@ def main():
                 "scan_code_object_sha": scan_code_object_hash(),
             },
         }
-        if world == 1 and not args.no_h2d:
+        full = args.full and world == 1
+        if full and not args.no_h2d:
             out["h2d_inclusive"] = h2d_inclusive(plan, state, args.seed)
-        if world == 1 and not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_rows, args.seed)
-        if world == 1 and args.workloads:
+        if full and args.workloads:
             del table, state, plan
             N.release_cached_memory()
             out["workloads"] = other_workloads(args, t_start)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+def dump_outputs(path: str, row) -> None:
+    """DIR/row.npy: what the last timed step returned to its caller -- one value per aggregation
+    of the plan in suite order (counts, sums and extremes; a StandardDeviation state is its
+    (n, avg, m2) triple), flattened to float64 with NaN for a NULL.  Counts stay below 2^53, so
+    float64 holds every value exactly.  The table is a pure function of --rows, --batch-rows and
+    --seed, so two builds run with the same arguments can be compared value for value."""
+    import numpy as np
+    flat = []
+    for v in row:
+        for x in (v if isinstance(v, tuple) else (v,)):
+            flat.append(float("nan") if x is None else float(x))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "row.npy"), np.asarray(flat, dtype=np.float64))
 
 
 WORKLOAD_CONFIG = {"c3": "configs[2]", "c4": "configs[3]", "c5": "configs[4]"}

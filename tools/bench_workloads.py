@@ -93,7 +93,8 @@ def run_single(workload: str, rows: int, steps: int, warmup: int, batch_rows: in
                cpu_rows=None, dev: str = "cuda:0") -> dict:
     """One workload on one GPU: builds its synthetic table in HBM, runs `warmup` untimed steps,
     times `steps` steps (wall clock between two device syncs, and HIP events on the stream per
-    step) and returns the JSON record.  bench.py calls it for configs[2]-[4] after its S10 leg."""
+    step) and returns the JSON record.  bench.py --full calls it for configs[2]-[4] after its S10
+    leg."""
     import torch
     from deequ_amd.synth import item_table_device
     if workload == "c5":
