@@ -11,5 +11,7 @@ from .runners import Analysis, AnalysisRunner, AnalyzerContext  # noqa: F401
 from .table import Table  # noqa: F401
 from .checks import Check, CheckLevel, CheckResult, CheckStatus, ConstraintStatus  # noqa: F401
 from .verification import VerificationResult, VerificationSuite  # noqa: F401
+from .schema import (RowLevelSchema, RowLevelSchemaValidationResult,  # noqa: F401
+                     RowLevelSchemaValidator, SchemaValueNotSupported)
 
 __version__ = "0.1.0"

@@ -104,6 +104,20 @@ class dq_freq_summary(Structure):
                 ("n_null_key_rows", c_int64), ("entropy", c_double)]
 
 
+# dq_schema_kind
+SCHEMA_STRING, SCHEMA_INT, SCHEMA_DECIMAL, SCHEMA_TIMESTAMP = range(1, 5)
+SELECT_TILE_ROWS = 16384  # DQ_SELECT_TILE_ROWS
+
+
+class dq_schema_column(Structure):
+    _fields_ = [("kind", c_int32), ("column", c_int32), ("is_nullable", c_int32),
+                ("has_min", c_int32), ("has_max", c_int32), ("min_value", c_int32),
+                ("max_value", c_int32), ("precision", c_int32), ("scale", c_int32),
+                ("regex_bytes", c_int32), ("regex", c_void_p), ("mask", c_void_p),
+                ("mask_tokens", c_int32), ("reserved", c_int32), ("cast_values", c_void_p),
+                ("cast_validity", c_void_p)]
+
+
 class EngineError(RuntimeError):
     """A non-OK dq_status, carrying the library's dq_last_error() message."""
 
@@ -177,6 +191,13 @@ def _load() -> ctypes.CDLL:
         "dq_decimal_to_double": (c_double, [c_uint64, c_int64, c_int32]),
         "dq_format_values": (c_int, [c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
         "dq_cast_utf8": (c_int, [POINTER(dq_column), c_int, c_void_p, c_void_p, POINTER(c_int64), c_void_p]),
+        "dq_schema_evaluate": (c_int, [POINTER(dq_schema_column), c_int, POINTER(dq_column), c_int,
+                                       c_int64, c_void_p, c_void_p, POINTER(c_int64),
+                                       POINTER(c_int64), POINTER(c_int64), c_void_p]),
+        "dq_select_plan": (c_int, [c_void_p, c_int64, c_void_p, c_int64, POINTER(c_int64),
+                                   POINTER(dq_column), c_int, POINTER(c_int64), c_void_p]),
+        "dq_gather_column": (c_int, [POINTER(dq_column), c_void_p, c_int64, POINTER(dq_column),
+                                     c_void_p]),
         "dq_freq_import": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                    c_int64, c_int, c_void_p]),
         "dq_freq_num_rows": (c_int64, [c_void_p]),
@@ -226,6 +247,7 @@ EXPORTED = [
     "dq_loader_destroy", "dq_loader_stage", "dq_loader_release", "dq_scan_host",
     "dq_freq_add_host", "dq_freq_partition_sizes", "dq_freq_partition",
     "dq_freq_add_records_device", "dq_key_partition",
+    "dq_schema_evaluate", "dq_select_plan", "dq_gather_column",
 ]
 FREQ_RECORD_BYTES = 24  # sizeof(dq_freq_record)
 

@@ -985,8 +985,8 @@ static dq_status upload_host(dq_state* s) {
 // states (status 1 sticky accept, 2 dead) made self-loops, then one flag byte per state -- bit 0:
 // accepted once the end-of-text symbol is read from it, bit 1: terminal.  False when the automaton
 // does not fit u8 states (the interpreter walks it instead).
-static bool build_regex_table(const std::string& pool, int64_t at, std::vector<uint8_t>& tab,
-                              int* ns_out, int* start_out) {
+bool dq::build_regex_table(const std::string& pool, int64_t at, std::vector<uint8_t>& tab,
+                           int* ns_out, int* start_out) {
   if (at < 0 || (size_t)at + 16 + 256 > pool.size()) return false;
   const uint8_t* blob = reinterpret_cast<const uint8_t*>(pool.data()) + at;
   int32_t head[4];

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -136,6 +137,10 @@ constexpr int kRegexMaxStates = 255;
 hipError_t launch_regex(const uint8_t* valid, const int32_t* offsets, const uint8_t* data,
                         int64_t rows, const uint8_t* table, int ns, int start, int null_mode,
                         uint64_t* out_val, uint64_t* out_vld, hipStream_t stream);
+// That table from a regex blob at pool[at] (api.cpp); false when the automaton does not fit u8
+// states or is malformed.  dq_schema_evaluate (rowschema.hip) builds its regex clauses with it.
+bool build_regex_table(const std::string& pool, int64_t at, std::vector<uint8_t>& tab, int* ns_out,
+                       int* start_out);
 // Body classes of the scan: one kernel instantiation each (scan.hip).
 enum BodyClass : int32_t {
   BC_NUM_I8 = 0,

@@ -541,6 +541,94 @@ dq_status dq_cast_utf8(const dq_column* in, int to_type, void* values_out, uint8
                        int64_t* n_unsupported, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Row-level schema validation (schema/RowLevelSchemaValidator.scala:183-281) and the row selection
+ * it needs: evaluate a schema over one batch of string columns, plan a selection from a row bitmap,
+ * gather columns through the planned index list.  Every buffer below is device memory that the
+ * caller allocates and owns; the library uses its cached-block allocator for scratch only.  All
+ * three entry points are ordered on `hip_stream` and synchronise it before they return, so their
+ * host outputs are final and their device outputs complete on return.  A batch has at most
+ * 2^31-1 rows (DQ_ERR_UNSUPPORTED beyond).
+ * ---------------------------------------------------------------------------------------------- */
+typedef enum dq_schema_kind {
+  DQ_SCHEMA_STRING = 1,   /* withStringColumn    :85-95   min / max = length bounds, regex        */
+  DQ_SCHEMA_INT = 2,      /* withIntColumn       :106-114 min / max = value bounds                */
+  DQ_SCHEMA_DECIMAL = 3,  /* withDecimalColumn   :125-133 precision, scale                        */
+  DQ_SCHEMA_TIMESTAMP = 4 /* withTimestampColumn :143-150 mask                                    */
+} dq_schema_kind;
+
+/* One ColumnDefinition (RowLevelSchemaValidator.scala:25-69) and where its cast goes. */
+typedef struct dq_schema_column {
+  int32_t kind;        /* dq_schema_kind                                                          */
+  int32_t column;      /* index into cols: a DQ_UTF8 column, declared at most once                */
+  int32_t is_nullable; /* 0 adds the clause `v IS NOT NULL`                                       */
+  int32_t has_min;     /* STRING: minLength given; INT: minValue given                            */
+  int32_t has_max;     /* STRING: maxLength given; INT: maxValue given                            */
+  int32_t min_value;
+  int32_t max_value;
+  int32_t precision;   /* DECIMAL: 1 <= precision <= 38, 0 <= scale <= precision                  */
+  int32_t scale;
+  int32_t regex_bytes; /* STRING: bytes of `regex`                                                */
+  const uint8_t* regex; /* STRING: host memory, an automaton in DQ_X_REGEX's layout
+                           (regex.py CompiledRegex.blob) of at most 255 states (more:
+                           DQ_ERR_UNSUPPORTED), or NULL for no `matches` clause                   */
+  const uint8_t* mask; /* TIMESTAMP: host memory, mask_tokens byte pairs (kind, value): kind 0 =
+                          the literal ASCII byte `value` (no digit); kinds 1..6 = the numeric field
+                          yyyy MM dd HH mm ss, value = its width (4 2 2 2 2 2), each at most once  */
+  int32_t mask_tokens; /* 1 .. 48                                                                 */
+  int32_t reserved;
+  void* cast_values;   /* INT / DECIMAL / TIMESTAMP: rows x int32 / 16-byte unscaled / int64 us,
+                          written for every row (0 where the cast is NULL); STRING: unused         */
+  uint64_t* cast_validity; /* the cast's validity, one uint64 word per 64 rows, LSB-first (an
+                          Arrow bitmap of (rows + 63) / 64 * 8 bytes), bits beyond rows zero     */
+} dq_schema_column;
+
+/* Evaluates toCNF (RowLevelSchemaValidator.scala:225-281) over one batch: cols[n_cols] are the
+ * batch's columns, rows its row count, defs[n_defs] the declared columns.  A row's verdict is the
+ * Kleene AND of every clause; valid_bitmap gets the rows whose verdict is TRUE, invalid_bitmap the
+ * rows where it is FALSE (a NULL verdict -- a NULL in a nullable int column with a minValue, line
+ * 246's `colIsNull.isNull` -- is in neither, as under where(cnf) / where(not(cnf)), :198, :222),
+ * *n_valid / *n_invalid their popcounts.  Both bitmaps hold (rows + 63) / 64 uint64 words, bit
+ * r % 64 of word r / 64 for row r, bits beyond rows zero.  Casts: Spark 2.2 UTF8String.toInt;
+ * new java.math.BigDecimal(s) then Decimal.changePrecision(p, s) (ROUND_HALF_UP);
+ * unix_timestamp(v, mask).cast(TimestampType) in UTC for values in strict form (every field its
+ * full width in digits and in range, literals byte-equal, nothing trailing, years 1583-9999).
+ * n_unsupported[n_defs] counts, per declared column, the values whose outcome under Java this
+ * engine does not decide (dq_cast_utf8's contract): a decimal string with a byte >= 0x80 or an
+ * exponent of more than 4 digits, a timestamp string that is neither in strict form nor certain to
+ * fail SimpleDateFormat's lenient parse.  Such rows are treated as failed casts; the caller must
+ * treat a non-zero count as a failure. */
+dq_status dq_schema_evaluate(const dq_schema_column* defs, int n_defs, const dq_column* cols,
+                             int n_cols, int64_t rows, uint64_t* valid_bitmap,
+                             uint64_t* invalid_bitmap, int64_t* n_valid, int64_t* n_invalid,
+                             int64_t* n_unsupported, void* hip_stream);
+
+/* Rows of one selection tile: the tile counts of a plan are one workgroup's popcounts each. */
+#define DQ_SELECT_TILE_ROWS 16384
+
+/* Plans the selection of the rows whose bit is set in `bitmap` (the layout above; bits beyond
+ * rows are ignored): the Filter of where(cnf) / where(not(cnf)) (:198, :222) as a stable index
+ * list, index_out[k] = the input row of output row k, ascending.  *n_selected is the number of set
+ * bits; when it exceeds index_capacity (the int32 entries index_out holds) nothing is written and
+ * DQ_ERR_INVALID_ARGUMENT returned with *n_selected set.  utf8_bytes_out[c] = the string bytes
+ * the selected rows of utf8_cols[c] (a column of `rows` rows) hold: the size of the data buffer a
+ * gather of that column needs.  Per-tile popcounts, an exclusive scan of them and the write are
+ * three launches; no workgroup waits on another. */
+dq_status dq_select_plan(const uint64_t* bitmap, int64_t rows, int32_t* index_out,
+                         int64_t index_capacity, int64_t* n_selected, const dq_column* utf8_cols,
+                         int n_utf8, int64_t* utf8_bytes_out, void* hip_stream);
+
+/* Gathers n_out rows of `in` through index[n_out] into the caller's buffers named by `out` (the
+ * projection of :217-222 after the filter; any column type of this header).  On entry out->type
+ * equals in->type, out->values holds n_out values (DQ_BOOL: (n_out + 63) / 64 * 8 bytes, written
+ * as whole words; DQ_UTF8: n_out + 1 int32 offsets starting at 0), out->data (DQ_UTF8) holds
+ * out->data_bytes bytes (DQ_ERR_INVALID_ARGUMENT when the gathered strings need more), and
+ * out->validity is (n_out + 63) / 64 * 8 bytes when in->validity is set and NULL when it is not.
+ * On return out->length = n_out and out->data_bytes = the string bytes written.  An index outside
+ * [0, in->length) reads nothing and yields a NULL / zero / empty row. */
+dq_status dq_gather_column(const dq_column* in, const int32_t* index, int64_t n_out,
+                           dq_column* out, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Columnar handoff: host-resident Arrow batches -> HBM (the JNI shim's entry).
  *
  * In the reference a Spark partition's rows stream through the aggregation iterator of the one
