@@ -569,14 +569,16 @@ extern "C" dq_status dq_plan_create(const dq_plan_desc* desc, dq_plan** out) {
   p->types.assign(desc->column_types, desc->column_types + desc->n_columns);
   for (int t : p->types)
     if (!valid_type(t)) return fail(DQ_ERR_INVALID_ARGUMENT, "unknown column type %d", t);
+  std::vector<char> too_deep;
   for (int e = 0; e < desc->n_exprs; ++e) {
     std::unique_ptr<Node> n;
     int pos = 0;
     if (!parse_node(desc->exprs[e].words, desc->exprs[e].n_words, pos, n, desc->n_columns, 0) ||
         pos != desc->exprs[e].n_words)
       return fail(DQ_ERR_INVALID_ARGUMENT, "malformed expression %d", e);
-    if (stack_depth(*n) > kMaxStack)
-      return fail(DQ_ERR_UNSUPPORTED, "expression %d nests deeper than %d", e, kMaxStack);
+    // (only the interpreter has a stack: a long list that fuses into a TK_STR_IN task never
+    // reaches it, so the depth is checked where an expression is materialised)
+    too_deep.push_back(stack_depth(*n) > kMaxStack);
     if (casts_string_to_float(*n, p->types))
       return fail(DQ_ERR_UNSUPPORTED, "expression %d casts a string to FLOAT", e);
     std::string why;
@@ -589,12 +591,17 @@ extern "C" dq_status dq_plan_create(const dq_plan_desc* desc, dq_plan** out) {
     if (c < 0 || c >= desc->n_columns) return fail(DQ_ERR_NO_SUCH_COLUMN, "no such column %d", c);
     return DQ_OK;
   };
+  auto materialise = [&](int expr, int& m) -> dq_status {
+    if (too_deep[expr])
+      return fail(DQ_ERR_UNSUPPORTED, "expression %d nests deeper than %d", expr, kMaxStack);
+    m = mat_index(p.get(), expr);
+    return DQ_OK;
+  };
   auto where_of = [&](const dq_agg& a, int& w) -> dq_status {
     w = -1;
     if (a.where < 0) return DQ_OK;
     if (a.where >= desc->n_exprs) return fail(DQ_ERR_INVALID_ARGUMENT, "bad where index");
-    w = mat_index(p.get(), a.where);
-    return DQ_OK;
+    return materialise(a.where, w);
   };
 
   for (const dq_agg& a : p->aggs) {
@@ -647,7 +654,7 @@ extern "C" dq_status dq_plan_create(const dq_plan_desc* desc, dq_plan** out) {
             TaskPlan b;
             b.kind = TK_BOOLMAP;
             b.where = w;
-            b.bool_expr = mat_index(p.get(), a.expr);
+            if ((st = materialise(a.expr, b.bool_expr)) != DQ_OK) return st;
             b.out = (int)p->tasks.size();
             p->tasks.push_back(b);
             s.task = b.out;
@@ -665,7 +672,7 @@ extern "C" dq_status dq_plan_create(const dq_plan_desc* desc, dq_plan** out) {
           TaskPlan t;
           t.kind = TK_BOOLMAP;
           t.where = w;
-          t.bool_expr = mat_index(p.get(), a.expr);
+          if ((st = materialise(a.expr, t.bool_expr)) != DQ_OK) return st;
           t.out = (int)p->tasks.size();
           p->tasks.push_back(t);
           s.task = t.out;

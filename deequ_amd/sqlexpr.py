@@ -16,7 +16,8 @@ CAST(x AS DOUBLE)) and applies Spark 2.2's type coercion so the engine only sees
   * numeric vs numeric: compared in the wider type (integral -> int64, else double);
   * string vs numeric: the string side is CAST to DOUBLE (Spark 2.2 ``PromoteStrings``);
   * ``x IN (...)`` with mixed item types: numeric literals in a string list become strings
-    (``InConversion`` -> ``findWiderCommonType`` with string promotion).
+    (``InConversion`` -> ``findWiderCommonType`` with string promotion); a numeric column or
+    cast IN a list of strings, which Spark casts to STRING row by row, raises :class:`SqlError`.
 
 Column names resolve case-insensitively (spark.sql.caseSensitive=false).  Anything outside the
 grammar raises :class:`SqlError`, which the runner turns into a failure of the shared scan exactly
@@ -429,6 +430,12 @@ class _Emitter:
                     target = "float" if "float" in kinds else "int"
                 else:
                     raise SqlError("incompatible types in IN list")
+            if target == "str" and tx not in ("str", "null") and x.op != "lit":
+                # Spark 2.2 InConversion casts the value to STRING (1 IN ('1', '2') is TRUE,
+                # 1 IN ('01') FALSE); the interpreter has no cast to string outside a regex, and
+                # comparing the number with the strings as they are would make every row FALSE
+                raise SqlError(f"a {tx} value IN a list of strings (Spark casts the value to "
+                               f"STRING) is not supported by the engine")
             w += [N.X_IN, len(items)]
             self.emit(x, target if target != tx or tx == "str" else None)
             for i in items:

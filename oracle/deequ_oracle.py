@@ -178,12 +178,21 @@ def parse_predicate(sql: str):
     return _P(_tokens(sql)).expr()
 
 
+_JAVA_DOUBLE = re.compile(r"^[+-]?(?:NaN|Infinity|(?:[0-9]+\.?[0-9]*|\.[0-9]+)(?:[eE][+-]?[0-9]+)?[fFdD]?)\Z")
+
+
 def _to_double(v):
+    """Spark 2.2 Cast(StringType -> DoubleType) is `s.toString.toDouble` with NULL on a
+    NumberFormatException, i.e. java.lang.Double.parseDouble: characters <= U+0020 trimmed, an
+    optional sign, `NaN` / `Infinity` in exactly that case, decimal digits with an optional
+    exponent and an optional f / F / d / D suffix ("1.5d" is 1.5).  Python's float() differs on
+    each of these ("nan", "inf", "1_0" parse, "1.5d" does not), so the grammar is restated here;
+    Java's hexadecimal floating-point strings are not."""
     if isinstance(v, str):
-        try:
-            return float(v.strip())
-        except ValueError:
+        s = v.strip("".join(chr(c) for c in range(33)))
+        if not _JAVA_DOUBLE.match(s):
             return None
+        return float(s.rstrip("fFdD") if s[-1] in "fFdD" else s)
     return float(v)
 
 
@@ -269,7 +278,23 @@ def eval_predicate(node, row: Dict[str, object]):
                 saw_null = True
                 continue
             if isinstance(x, str) != isinstance(it, str):
-                it = str(it) if isinstance(x, str) else it
+                # Spark 2.2 InConversion (TypeCoercion.scala): findWiderCommonType promotes a
+                # numeric / string mix to StringType and casts BOTH sides to it, so a number meets
+                # a string item as its cast to string -- 1 IN ('1') is TRUE, 1 IN ('01') and
+                # 1 IN ('1.0') are FALSE (a double prints as Double.toString; a float column's
+                # Float.toString is not restated: rows carry no column types here)
+                if isinstance(x, str):
+                    it = str(it)
+                elif isinstance(x, bool):
+                    raise ValueError("boolean IN (strings): Spark raises an AnalysisException")
+                elif isinstance(x, float):
+                    if java_double_to_string(x) == it:
+                        return True
+                    continue
+                else:
+                    if str(x) == it:
+                        return True
+                    continue
             if _cmp3(x, it) == 0:
                 return True
         return None if saw_null else False
