@@ -5,23 +5,35 @@
 // top-N (Histogram.scala:78-79).
 //
 // A radix-partitioned group-by, so that every pass streams HBM and every count happens in LDS
-// (random HBM atomics into a billion-slot table ran at 1.4 % of HBM peak in round 1):
+// (random HBM atomics into a billion-slot table ran at 1.4 % of HBM peak in round 1).
 //
-//   phase A (per added batch; freq_phaseA): one 1024-thread workgroup per chunk of 8192 rows
-//     (4096 in hashed mode).  Each row's key is hashed (freq_codec.h); the first 1024 rows of the
-//     chunk go through a 2048-slot LDS table that collapses repeated keys (bypassed for the rest
-//     of the chunk when fewer than 1/16 of them repeated, i.e. high-cardinality keys), and every
-//     resulting record is counting-sorted in LDS by the top 9 bits of its hash (512 buckets) and
-//     written out as ONE contiguous chunk region plus a 513-entry u16 bucket histogram.
-//   phase B (finalize; freq_phaseB): the chunk histograms are transposed and scanned per bucket;
-//     a bucket's records are cut into units of ~kTile/2 records (whole chunk segments), and each
-//     unit is counting-sorted by the next s hash bits (s chosen so that a final partition holds a
-//     few thousand groups) into a contiguous output plus its sub-bucket histogram.
-//   phase C (finalize; freq_phaseC): one workgroup per partition (bucket, sub-bucket) gathers its
-//     pieces of every unit of the bucket and counts them in an LDS hash table (8192 slots exact,
-//     4608 hashed), then emits the partition's Σ[c==1], #groups and entropy partial, optionally
-//     its top-4 groups (Histogram) or every group (export, merge, repartition).  A partition whose
-//     groups do not fit is recounted in 2, 4, ... passes over disjoint hash subsets.
+// Phase A (per added batch) hashes each row's key (freq_codec.h), collapses repeated keys in a
+// small LDS table that persists over a workgroup's tiles (bypassed while fewer than 1/16 of the
+// probed rows repeat), and writes one record per remaining row or collapsed group, grouped by the
+// top 9 hash bits (512 buckets).  Exact rows: freq_phaseA_xp writes each workgroup's records of a
+// bucket into a bucket piece, of fixed capacity (overflow goes to the tile's chunk) or laid out by
+// freq_prepass_x / freq_prepass_scan; a batch of integers in a narrow range is counted by value
+// instead (freq_dense_count / freq_dense_sum / freq_dense_emit).  One utf8 column:
+// freq_phaseA_small tries the batch first (few short keys, merged across workgroups), then
+// freq_phaseA<true, false, true> writes fixed-capacity pieces or bucket-sorted chunks.  Several
+// key columns: freq_phaseA<true, false>.  Records in (merge, repartition, marginals):
+// freq_phaseA<HASHED, true>.  A chunk is a tile's region plus a 513-entry u16 bucket histogram.
+//
+// Phase B (finalize) lists every bucket's segments -- chunk runs (freq_hist_transpose) and pieces
+// (freq_piece_transpose), scanned by freq_seg_scan -- cuts a bucket's records into units of one
+// exact or two hashed tiles (freq_unit_map), and counting-sorts each unit by the next s hash bits
+// (s chosen so that a final partition holds a few thousand records) with freq_phaseB_scatter_u.
+// Exact tables place the units' runs in partitions of fixed capacity through atomic cursors
+// (freq_cap_layout); hashed tables, and an exact table whose runs overflowed, count first
+// (freq_phaseB_count_w, freq_phaseB_scan, freq_part_scan).
+//
+// Phase C (finalize) counts each partition in an LDS hash table with persistent workgroups and
+// emits its sum of [c == 1], number of groups and entropy partial, optionally its top-4 groups
+// (Histogram) or every group (export, merge, repartition): freq_phaseC_x for exact tables (packed
+// one-word slots in the first pass when the counts fit), freq_phaseC_h for a hashed table's first
+// pass.  A partition whose groups do not fit is recounted in 2, 4, ... passes over disjoint hash
+// subsets (freq_phaseC_x, or freq_phaseC for hashed tables); freq_reduce_part / _final sum the
+// partitions' statistics in a fixed order.
 //
 // Exact mode (one fixed-width key) carries 8-byte records (h << 8 | count digit) whose hash is a
 // bijection of the value; hashed mode (strings, several keys, Histogram on strings) carries
@@ -50,21 +62,6 @@
 #include "freq_codec.h"
 #include "kernels.h"
 #include "stream_load.h"
-
-// freq_phaseC_x's probe rounds: branch-light (1) or round 5's per-record branches (0, a build
-// for A/B runs through DQ_LIB_PATH)
-#ifndef DQ_LEAN_PROBE
-#define DQ_LEAN_PROBE 1
-#endif
-#ifndef DQ_C_EXPERIMENT  // timing builds only (wrong results): 1 no statistics, 2 no inserts
-#define DQ_C_EXPERIMENT 0
-#endif
-#ifndef DQ_AX_EXPERIMENT  // timing builds only (wrong results): freq_phaseA_xp 1 no record stores,
-#define DQ_AX_EXPERIMENT 0  // 2 no counting sort (records in row order), 3 neither
-#endif
-#ifndef DQ_A_NOCOPY  // timing builds only (wrong results): phase A writes no arena key bytes
-#define DQ_A_NOCOPY 0
-#endif
 
 namespace dq {
 
@@ -96,19 +93,18 @@ template <>
 struct FM<false> {
   static constexpr int kTile = 8192;    // rows (and at most records) per phase-A chunk
   static constexpr int kRB = 8;         // bytes per record
-  static constexpr int kDedupe = 2048;  // phase-A LDS table slots
   static constexpr int kTableC = 4096;  // phase-C LDS table slots (two workgroups per CU)
   static constexpr int kTarget = 2000;  // records per final partition the sizing aims at
+  // records per partition of a table one level shallower that stays packed (finalize_b)
+  static constexpr uint64_t kTargetPk = 3700;
 };
 template <>
 struct FM<true> {
   static constexpr int kTile = 2048;
   static constexpr int kRB = 16;
-  static constexpr int kDedupe = 1024;
   static constexpr int kTableC = 2560;
   // (freq_phaseC_h takes up to 4096 records and 3584 groups per partition: ~1900-record partitions
-  // halve its per-item costs against ~950, configs[4] 176.3 -> 171.5 ms, A/B
-  // DQ_FREQ_PARTITION_TARGET_H)
+  // halve its per-item costs against ~950, configs[4] 176.3 -> 171.5 ms)
   static constexpr int kTarget = 2400;
 };
 // records per phase-B unit (whole chunk segments of one bucket): hashed two tiles (~32 records per
@@ -517,9 +513,7 @@ __global__ void __launch_bounds__((AKeys<HASHED, FROM_REC>::kThreads),
   // the instruction cache).
   __shared__ uint64_t stash[T * W];
   __shared__ uint64_t scnt[FROM_REC ? kThreads : 1];
-  // exact rows into bucket pieces (a.pstart): each bucket's next record slot in the batch region
-  constexpr bool XP = !HASHED && !FROM_REC;
-  __shared__ uint32_t wcur[XP ? kBuckets : 1];
+  static_assert(HASHED || FROM_REC, "exact rows go through freq_phaseA_xp");
   // STR1 rows into fixed-capacity bucket pieces: each piece's fill (u16: the LDS of two
   // workgroups per CU has 1.7 KB left)
   __shared__ uint16_t wfill[STR1 ? kBuckets : 1];
@@ -565,27 +559,6 @@ __global__ void __launch_bounds__((AKeys<HASHED, FROM_REC>::kThreads),
       const unsigned long long base = need ? atomicAdd(a.arena_cursor, (unsigned long long)need) : 0ULL;
       s_arena_base = (base + 15ULL) & ~15ULL;
       s_arena_cur = 0;
-    }
-  }
-  const bool pieces = XP && a.pstart != nullptr;
-  if constexpr (XP) {
-    if (pieces) {
-      // bucket b of the batch starts at the prefix of the batch's bucket totals; this workgroup's
-      // piece of it at the prefix of the earlier workgroups' rows of b (freq_prepass_scan)
-      uint32_t all;
-      const uint32_t tot = tid < kBuckets ? a.ptot[tid] : 0u;
-      const uint32_t bb = block_excl_scan(tot, s_wave, all);
-      if (tid < kBuckets) {
-        const uint32_t st = bb + a.ph[(int64_t)blockIdx.x * kBuckets + tid];
-        wcur[tid] = st;
-        a.pstart[(int64_t)blockIdx.x * kBuckets + tid] = st;
-      }
-      // the batch's chunk rows (tiles and workgroup chunks) hold no records: empty histograms
-      const int64_t nt = (a.n_items + a.tile_items - 1) / a.tile_items;
-      const int64_t r1 = min((int64_t)(blockIdx.x + 1) * a.tiles_per_wg, nt);
-      for (int64_t r = (int64_t)blockIdx.x * a.tiles_per_wg; r < r1; ++r)
-        for (int i = tid; i < kHistRow; i += kThreads) a.hist[r * kHistRow + i] = 0;
-      for (int i = tid; i < kHistRow; i += kThreads) a.hist[(nt + blockIdx.x) * kHistRow + i] = 0;
     }
   }
   unsigned long long nulls = 0, nullg = 0;
@@ -670,9 +643,9 @@ __global__ void __launch_bounds__((AKeys<HASHED, FROM_REC>::kThreads),
     const uint64_t off = s_arena_base + atomicAdd(&s_arena_cur, (unsigned long long)sz);
     if constexpr (STR1) {
       const SView v = str1_view(a.ks, row);
-      if (!DQ_A_NOCOPY) str1_encode_copy(v.p, v.len, reinterpret_cast<uint32_t*>(a.arena + off));
+      str1_encode_copy(v.p, v.len, reinterpret_cast<uint32_t*>(a.arena + off));
     } else {
-      if (!DQ_A_NOCOPY) row_encode_dw(a.ks, row, reinterpret_cast<uint32_t*>(a.arena + off));
+      row_encode_dw(a.ks, row, reinterpret_cast<uint32_t*>(a.arena + off));
     }
     return off;
   };
@@ -688,7 +661,7 @@ __global__ void __launch_bounds__((AKeys<HASHED, FROM_REC>::kThreads),
       if (k1 != kNoShort) {
         const uint64_t off = s_arena_base +
             atomicAdd(&s_arena_cur, (unsigned long long)(8 + pad4(str1_short_len(k1))));
-        if (!DQ_A_NOCOPY) str1_encode_short(k0, k1, reinterpret_cast<uint32_t*>(a.arena + off));
+        str1_encode_short(k0, k1, reinterpret_cast<uint32_t*>(a.arena + off));
         return off;
       }
     }
@@ -790,54 +763,6 @@ __global__ void __launch_bounds__((AKeys<HASHED, FROM_REC>::kThreads),
         stash[q * W] = HASHED ? r.key : fmix_bij(r.key);
         if (HASHED) stash[q * W + 1] = a.var_arena_base + (uint64_t)seg_var_base(a.segs, i) + r.enc_off;
         if (r.count) keyed |= 1u << j;
-      }
-    } else if constexpr (!HASHED) {  // one fixed-width column
-      // branch-free loads (an out-of-tile lane re-reads the tile's last row): a divergent branch
-      // around a load makes the compiler wait for it before the join
-      const KeyCol& c = a.ks.cols[0];
-      int64_t ic[ROUNDS];
-      uint32_t ok = 0;
-#pragma unroll
-      for (int j = 0; j < ROUNDS; ++j) {
-        const int64_t i = i0 + (int64_t)j * kThreads + tid;
-        ok |= (i < i1 ? 1u : 0u) << j;
-        ic[j] = i < i1 ? i : i1 - 1;
-      }
-      uint32_t vb = ~0u;
-      if (c.valid) {
-        uint32_t byte[ROUNDS];
-#pragma unroll
-        for (int j = 0; j < ROUNDS; ++j) byte[j] = c.valid[ic[j] >> 3];
-        vb = 0;
-#pragma unroll
-        for (int j = 0; j < ROUNDS; ++j) vb |= ((byte[j] >> (ic[j] & 7)) & 1u) << j;
-      }
-      uint64_t v[ROUNDS];
-      auto load_all = [&](auto type_tag) {
-        constexpr int TY = decltype(type_tag)::value;
-#pragma unroll
-        for (int j = 0; j < ROUNDS; ++j) v[j] = kwiden(TY, c.values, ic[j]);
-      };
-      switch (c.type) {  // block-uniform: one unrolled load loop per width
-        case DQ_INT8: load_all(std::integral_constant<int, DQ_INT8>{}); break;
-        case DQ_INT16: load_all(std::integral_constant<int, DQ_INT16>{}); break;
-        case DQ_INT32: load_all(std::integral_constant<int, DQ_INT32>{}); break;
-        case DQ_FLOAT32: load_all(std::integral_constant<int, DQ_FLOAT32>{}); break;
-        case DQ_FLOAT64: load_all(std::integral_constant<int, DQ_FLOAT64>{}); break;
-        case DQ_BOOL: load_all(std::integral_constant<int, DQ_BOOL>{}); break;
-        default: load_all(std::integral_constant<int, DQ_INT64>{}); break;
-      }
-#pragma unroll
-      for (int j = 0; j < ROUNDS; ++j) {
-        if (!((ok >> j) & 1u)) continue;
-        if ((vb >> j) & 1u) {
-          keyed |= 1u << j;
-          stash[(j * kThreads + tid) * W] = fmix_bij(exact_canon(a.ks, v[j]));
-        } else {
-          const unsigned long long ng = a.ks.null_as_group ? 1ULL : 0ULL;
-          nullg += ng;
-          nulls += 1ULL - ng;
-        }
       }
     } else if constexpr (STR1) {  // one utf8 column: offsets, then <= 16 bytes per row, then hash
       const KeyCol& c = a.ks.cols[0];
@@ -1079,8 +1004,7 @@ __global__ void __launch_bounds__((AKeys<HASHED, FROM_REC>::kThreads),
     mark(t, 2);
     if (!any_raw) {  // every row collapsed into the dedupe table: an empty chunk, no sort
       uint16_t* hrow = a.hist + t * kHistRow;
-      if (!pieces)
-        for (int i = tid; i < kHistRow; i += kThreads) hrow[i] = 0;
+      for (int i = tid; i < kHistRow; i += kThreads) hrow[i] = 0;
       mark(t, 3);
       mark(t, 4);
       continue;
@@ -1110,75 +1034,10 @@ __global__ void __launch_bounds__((AKeys<HASHED, FROM_REC>::kThreads),
         }
     }
     // 3. counting sort of the raw rows into the tile's chunk
-    if constexpr (XP) {
-      if (pieces) {
-        // ... or, bucket pieces: sorted in LDS by bucket, then written to each bucket's next
-        // slots in the batch region (runs of ~16 records per bucket and tile, each continuing
-        // the workgroup's piece of that bucket)
-        __syncthreads();
-        uint32_t ctotal;
-        const uint32_t cnt = tid < kBuckets ? bh[tid] : 0u;
-        const uint32_t ex = block_excl_scan(cnt, s_wave, ctotal);
-        if (tid < kBuckets) bcur[tid] = ex;
-        __syncthreads();
-        mark(t, 3);
-        uint32_t pv[ROUNDS];
-        uint64_t hv[ROUNDS];
-#pragma unroll
-        for (int j = 0; j < ROUNDS; ++j) {
-          if (!((raw >> j) & 1u)) continue;
-          hv[j] = stash[j * kThreads + tid];
-          pv[j] = atomicAdd(&bcur[bucket_of(hv[j])], 1u);
-        }
-        __syncthreads();
-        if (tid < kBuckets) {  // bcur: the bucket's region slot minus its first sorted position
-          const uint32_t c = bh[tid], st = bcur[tid] - c;
-          bcur[tid] = wcur[tid] - st;
-          wcur[tid] += c;
-        }
-#pragma unroll
-        for (int j = 0; j < ROUNDS; ++j)
-          if ((raw >> j) & 1u) stash[pv[j]] = hv[j];
-        __syncthreads();
-        uint64_t* out = reinterpret_cast<uint64_t*>(a.recs);
-        for (uint32_t i = tid; i < ctotal; i += kThreads) {
-          const uint64_t hh = stash[i];
-          out[(uint32_t)(bcur[bucket_of(hh)] + i)] = (hh << 8) | 1u;  // the count-1 digit code
-        }
-        end_chunk();
-        mark(t, 4);
-        continue;
-      }
-    }
-    uint32_t ctotal = 0;
     if (STR1 && hpieces) begin_tile_pieces(t);
-    else ctotal = begin_chunk(t, need);
+    else begin_chunk(t, need);
     mark(t, 3);
-    if constexpr (!HASHED && !FROM_REC) {
-      // exact rows (count 1: one record each): sorted in LDS over the stash, then written out as
-      // one contiguous 16-byte-store stream (scattered 8-byte global stores were ~half the tile)
-      uint64_t rv[ROUNDS];
-      uint32_t pv[ROUNDS];
-#pragma unroll
-      for (int j = 0; j < ROUNDS; ++j) {
-        if (!((raw >> j) & 1u)) continue;
-        const uint64_t h = stash[j * kThreads + tid];
-        pv[j] = atomicAdd(&bcur[bucket_of(h)], 1u);
-        rv[j] = (h << 8) | 1u;  // the count-1 digit code (for_digits(1))
-      }
-      __syncthreads();
-#pragma unroll
-      for (int j = 0; j < ROUNDS; ++j)
-        if ((raw >> j) & 1u) stash[pv[j]] = rv[j];
-      __syncthreads();
-      uint64_t* out = reinterpret_cast<uint64_t*>(a.recs) + t * (int64_t)T;
-      const uint32_t pairs = ctotal >> 1;
-      for (uint32_t i = tid; i < pairs; i += kThreads) {
-        const ulonglong2 v = make_ulonglong2(stash[2 * i], stash[2 * i + 1]);
-        reinterpret_cast<ulonglong2*>(out)[i] = v;
-      }
-      if ((ctotal & 1u) && tid == 0) out[ctotal - 1] = stash[ctotal - 1];
-    } else if (HASHED && !FROM_REC && !STR1 && str2) {
+    if (HASHED && !FROM_REC && !STR1 && str2) {
       // two utf8 columns: each round's arena bytes (one LDS atomic per wave and round) and
       // encodings
       constexpr int G = 2;  // rounds whose values are in flight together (again: L2 hits)
@@ -1205,7 +1064,7 @@ __global__ void __launch_bounds__((AKeys<HASHED, FROM_REC>::kThreads),
                   (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)wbase, 63);
           if (!on) continue;
           const uint64_t off = s_arena_base + wbase + (incl - sz);
-          if (!DQ_A_NOCOPY) str2_encode(a.ks, x[g], reinterpret_cast<uint32_t*>(a.arena + off));
+          str2_encode(a.ks, x[g], reinterpret_cast<uint32_t*>(a.arena + off));
           put(t, stash[q * W], 1u, off);
         }
       }
@@ -1231,13 +1090,13 @@ __global__ void __launch_bounds__((AKeys<HASHED, FROM_REC>::kThreads),
         const uint64_t off = s_arena_base + wbase + (incl - sz);
         if constexpr (STR1) {
           if (k1 != kNoShort) {
-            if (!DQ_A_NOCOPY) str1_encode_short16(k0, k1, reinterpret_cast<uint32_t*>(a.arena + off));
+            str1_encode_short16(k0, k1, reinterpret_cast<uint32_t*>(a.arena + off));
           } else {
-            if (!DQ_A_NOCOPY) str1_encode_copy16(a.ks.cols[0].data + (uint32_t)k0, (int32_t)(k0 >> 32),
+            str1_encode_copy16(a.ks.cols[0].data + (uint32_t)k0, (int32_t)(k0 >> 32),
                                reinterpret_cast<uint32_t*>(a.arena + off));
           }
         } else {
-          if (!DQ_A_NOCOPY) row_encode_dw(a.ks, row, reinterpret_cast<uint32_t*>(a.arena + off));
+          row_encode_dw(a.ks, row, reinterpret_cast<uint32_t*>(a.arena + off));
         }
         if (STR1 && hpieces) put_pieces(t, stash[q * W], 1u, off);
         else put(t, stash[q * W], 1u, off);  // (row keys: one record, the count-1 digit code)
@@ -1255,31 +1114,6 @@ __global__ void __launch_bounds__((AKeys<HASHED, FROM_REC>::kThreads),
     }
     end_chunk();
     mark(t, 4);
-  }
-  if constexpr (XP) {
-    if (pieces) {  // the collapsed groups into their buckets' pieces, then the pieces' lengths
-      uint64_t* out = reinterpret_cast<uint64_t*>(a.recs);
-      __syncthreads();
-      for (int sl = tid; sl < D; sl += kThreads) {
-        const uint64_t k = dkey[sl];
-        if (k == kEmptyKey) continue;
-        const uint32_t b = bucket_of(k);
-        maxcnt = dcnt[sl] > maxcnt ? dcnt[sl] : maxcnt;
-        for_digits(dcnt[sl], [&](uint32_t code) { out[atomicAdd(&wcur[b], 1u)] = (k << 8) | code; });
-      }
-      wave_max_lds(&s_maxcnt, maxcnt);
-      __syncthreads();
-      if (tid == 0 && s_maxcnt) atomicMax(&a.counters[C_MAXCNT], s_maxcnt);
-      if (tid < kBuckets)
-        a.plen[(int64_t)blockIdx.x * kBuckets + tid] =
-            wcur[tid] - a.pstart[(int64_t)blockIdx.x * kBuckets + tid];
-      wave_count(&a.counters[C_NULL_ROWS], nulls);
-      wave_count(&a.counters[C_NULL_GROUP], nullg);
-      __syncthreads();
-      if (tid < 3 && s_dbg[tid]) atomicAdd(&a.counters[C_DBG_NOTREADY + tid], (unsigned long long)s_dbg[tid]);
-      wave_count(&a.counters[C_DBG_BYPASS], dbg_bypass);
-      return;
-    }
   }
   // the collapsed groups of the whole range -> this workgroup's own chunk
   uint64_t need = 0;
@@ -1322,8 +1156,8 @@ __global__ void __launch_bounds__((AKeys<HASHED, FROM_REC>::kThreads),
 // Phase A0, exact rows: the rows of each phase-A workgroup per bucket, so that phase A can write
 // the batch bucket-major (bucket b of the batch is one contiguous region when no rows collapse in
 // the dedupe table, and phase B then reads whole buckets as streams instead of gathering 128-byte
-// chunk segments).  Same tile ranges and the same hash as freq_phaseA<false, false>; only
-// non-NULL rows are keyed.
+// chunk segments).  Same tile ranges and the same hash as freq_phaseA_xp; only non-NULL rows are
+// keyed.
 // ------------------------------------------------------------------------------------------------
 // row base + r of a fixed-width column, the base (wave-uniform) applied to the pointer
 template <int TY>
@@ -1434,11 +1268,11 @@ __global__ void __launch_bounds__(kPreThreads) freq_prepass_x(AArgs a, uint32_t*
 }
 
 // ------------------------------------------------------------------------------------------------
-// Phase A, exact rows into bucket pieces (the pieces layout of freq_phaseA<false, false> with
-// a.pstart set; same tile ranges, dedupe table and bypass probing, same records).  A lean kernel
-// of its own: 512 threads x 16 rounds per 8192-row tile and ~80 KB of LDS, so TWO workgroups
-// share a CU and one's loads overlap the other's sort and stores (the generic kernel, 1024 threads
-// at 128 VGPRs with spills, ran one workgroup per CU with every phase behind a barrier).  The
+// Phase A, exact rows into bucket pieces (freq_phaseA's tile ranges, dedupe table and bypass
+// probing).  A lean kernel of its own: 512 threads x 16 rounds per 8192-row tile and ~80 KB of
+// LDS, so TWO workgroups share a CU and one's loads overlap the other's sort and stores (exact
+// rows through freq_phaseA, 1024 threads at 128 VGPRs with spills, ran one workgroup per CU with
+// every phase behind a barrier).  The
 // bucket-counting atomic returns the row's rank in its bucket, so the counting sort takes one LDS
 // atomic per row instead of two.
 // ------------------------------------------------------------------------------------------------
@@ -1625,15 +1459,6 @@ __global__ void __launch_bounds__(kAXThreads, 4) freq_phaseA_xp(AArgs a) {  // 4
         }
       }
       if (!__syncthreads_or(raw ? 1 : 0)) continue;  // every row collapsed: nothing to write
-#if DQ_AX_EXPERIMENT & 2  // (timing only: no counting sort -- the tile's records in row order)
-      {
-#pragma unroll
-        for (int j = 0; j < R; ++j)
-          if (!(DQ_AX_EXPERIMENT & 1) && ((raw >> j) & 1u))
-            out[a.piece_base + (uint64_t)t * T + (uint64_t)(j * kAXThreads + tid)] = (h[j] << 8) | 1u;
-        continue;
-      }
-#endif
       // 3. counting sort by bucket: the counting atomic gives each raw row its rank
       uint32_t rk[R];
 #pragma unroll
@@ -1674,8 +1499,7 @@ __global__ void __launch_bounds__(kAXThreads, 4) freq_phaseA_xp(AArgs a) {  // 4
         auto put = [&](uint32_t i) {
           const uint64_t hh = stash[i];
           const uint32_t b = bucket_of(hh);
-          if (!(DQ_AX_EXPERIMENT & 1))  // (timing builds: 1 = no record stores)
-            out[(uint32_t)((i < bh[b] ? gdel[b] : odel[b]) + i)] = (hh << 8) | 1u;
+          out[(uint32_t)((i < bh[b] ? gdel[b] : odel[b]) + i)] = (hh << 8) | 1u;
         };
         // int64 keys: four records' LDS reads in flight per step (422 -> 414-419 us per configs[2]
         // batch, profiles/r6ak/); the other widths spill with it.  (Fully unrolled -- every
@@ -2524,55 +2348,14 @@ DQ_DEV int64_t window_rec(const UnitLds& L, uint32_t nwin, uint32_t li) {
   return (int64_t)L.sw_s[j] + (li - L.sw_pos[j]);
 }
 
-// Calls f(record words) for every record of the unit.  Every thread of the block must call it.
-// Each thread loads PB records before it uses any (one HBM round trip per PB records; an
-// out-of-range lane re-reads the window's last record and drops it).
-template <bool HASHED, typename F>
-DQ_DEV void for_unit_records(const BArgs& a, UnitLds& L, F&& f) {
-  constexpr int W = FM<HASHED>::kRB / 8, PB = 8;
-  const int tid = threadIdx.x;
-  for (int64_t cw = L.s_c0; cw < L.s_c1; cw += kThreads) {
-    uint32_t nwin;
-    const uint32_t wtot = unit_window(a, L, cw, nwin);
-    for (uint32_t base = 0; base < wtot; base += (uint32_t)PB * kThreads) {
-      uint64_t rv[PB][W];
-#pragma unroll
-      for (int k = 0; k < PB; ++k) {
-        uint32_t li = base + (uint32_t)k * kThreads + tid;
-        li = li < wtot ? li : wtot - 1;
-        const uint64_t* src = reinterpret_cast<const uint64_t*>(a.recs) + window_rec(L, nwin, li) * W;
-#pragma unroll
-        for (int x = 0; x < W; ++x) rv[k][x] = src[x];
-      }
-#pragma unroll
-      for (int k = 0; k < PB; ++k)
-        if (base + (uint32_t)k * kThreads + tid < wtot) f(rv[k]);
-    }
-    __syncthreads();
-  }
-}
-
 DQ_DEV uint32_t rec_sub(const uint64_t* r, int s, bool hashed) {
   return sub_of(hashed ? r[0] : (r[0] >> 8), s);
-}
-
-// B1: per unit, records per sub-bucket
-template <bool HASHED>
-__global__ void __launch_bounds__(kThreads) freq_phaseB_count(BArgs a) {
-  __shared__ UnitLds L;
-  __shared__ uint32_t sh[1 << kMaxSubBits];
-  const int S = 1 << a.s;
-  for (int i = threadIdx.x; i < S; i += kThreads) sh[i] = 0;
-  unit_range(a, blockIdx.x, L);
-  for_unit_records<HASHED>(a, L, [&](const uint64_t* r) { atomicAdd(&sh[rec_sub(r, a.s, HASHED)], 1u); });
-  uint32_t* row = a.uhist + (int64_t)blockIdx.x * S;
-  for (int i = threadIdx.x; i < S; i += kThreads) row[i] = sh[i];
 }
 
 // B1, one wave per unit: the sixteen waves of a workgroup count sixteen units each on its own, in
 // a histogram of its own in LDS, with no block barrier -- a unit's chain of dependent loads
 // (unit -> bucket -> segments -> records) overlaps fifteen others' instead of stalling its
-// workgroup (one unit per 1024-thread workgroup left ~two chains in flight per CU).  Same counts.
+// workgroup (one unit per 1024-thread workgroup left ~two chains in flight per CU).
 constexpr int kBcWaves = 16;
 template <bool HASHED>
 __global__ void __launch_bounds__(kBcWaves * 64) freq_phaseB_count_w(BArgs a) {
@@ -2676,90 +2459,10 @@ __global__ void __launch_bounds__(kThreads) freq_part_scan(unsigned long long* v
   (void)s_wave;
 }
 
-// B3: scatter every record of the unit to its partition, staged in LDS: each round of up to SUB
-// records is counting-sorted by sub-bucket in LDS, then written out in staged order, so the lanes
-// of a wave write runs of neighbouring addresses (a sub-bucket's records of the round) instead of
-// 64 scattered 8-byte stores to 64 partitions.
-// SUBB: staged bytes' worth of 8-byte words per round (8192: 64 KB staged, one workgroup per
-// CU; 4096: 32 KB, two per CU so one's loads overlap the other's sort and stores)
-template <bool HASHED, int SUBB = 8192>
-__global__ void __launch_bounds__(kThreads) freq_phaseB_scatter(BArgs a) {
-  constexpr int W = FM<HASHED>::kRB / 8;
-  constexpr int SUB = SUBB / W;  // records per round
-  constexpr int PER = SUB / kThreads;
-  constexpr int SMAX = 1 << kMaxSubBits;
-  __shared__ UnitLds L;
-  __shared__ unsigned long long cur[SMAX];  // the unit's next output position per sub-bucket
-  __shared__ unsigned long long gbs[SMAX];  // this round's output base per sub-bucket
-  __shared__ uint32_t hcnt[SMAX];           // this round's count, then local base, per sub-bucket
-  __shared__ uint64_t staged[SUB * W];
-  __shared__ uint16_t ssb[SUB];
-  // XCD-contiguous units: workgroup g runs on XCD g % 8; XCD x takes units [x*q, (x+1)*q)
-  const uint32_t g = blockIdx.x, q = (a.n_units + 7) / 8;
-  const uint32_t w = (g & 7u) * q + (g >> 3);
-  if (w >= a.n_units) return;
-  const int S = 1 << a.s;
-  const int tid = threadIdx.x;
-  unit_range(a, w, L);
-  const uint32_t* row = a.uhist + (int64_t)w * S;
-  for (int i = tid; i < S; i += kThreads) cur[i] = a.part_base[(uint64_t)L.s_b * S + i] + row[i];
-  uint64_t* out = reinterpret_cast<uint64_t*>(a.recsB);
-  for (int64_t cw = L.s_c0; cw < L.s_c1; cw += kThreads) {  // windows of segments
-    uint32_t nwin;
-    const uint32_t wtot = unit_window(a, L, cw, nwin);
-    for (uint32_t base = 0; base < wtot; base += SUB) {
-      const uint32_t nr = min((uint32_t)SUB, wtot - base);
-      for (int i = tid; i < S; i += kThreads) hcnt[i] = 0;
-      __syncthreads();
-      uint64_t rv[PER][W];
-      uint32_t sbv[PER], lpos[PER];
-#pragma unroll
-      for (int k = 0; k < PER; ++k) {
-        const uint32_t r = (uint32_t)k * kThreads + tid;
-        sbv[k] = 0;
-        if (r >= nr) continue;
-        const uint64_t* src = reinterpret_cast<const uint64_t*>(a.recs) + window_rec(L, nwin, base + r) * W;
-#pragma unroll
-        for (int x = 0; x < W; ++x) rv[k][x] = src[x];
-        sbv[k] = rec_sub(rv[k], a.s, HASHED);
-        lpos[k] = atomicAdd(&hcnt[sbv[k]], 1u);
-      }
-      __syncthreads();
-      const uint32_t cnt = tid < S ? hcnt[tid] : 0u;
-      uint32_t tot;
-      const uint32_t ex = block_excl_scan(cnt, L.s_wave, tot);  // (barriers: every count is read)
-      if (tid < S) {
-        hcnt[tid] = ex;
-        gbs[tid] = cur[tid];
-        cur[tid] += cnt;
-      }
-      __syncthreads();
-#pragma unroll
-      for (int k = 0; k < PER; ++k) {
-        const uint32_t r = (uint32_t)k * kThreads + tid;
-        if (r >= nr) continue;
-        const uint32_t slot = hcnt[sbv[k]] + lpos[k];
-#pragma unroll
-        for (int x = 0; x < W; ++x) staged[slot * W + x] = rv[k][x];
-        ssb[slot] = (uint16_t)sbv[k];
-      }
-      __syncthreads();
-      for (uint32_t i = tid; i < nr; i += kThreads) {
-        const uint32_t sb = ssb[i];
-        const unsigned long long d = gbs[sb] + (i - hcnt[sb]);
-#pragma unroll
-        for (int x = 0; x < W; ++x) out[d * W + x] = staged[i * W + x];
-      }
-      __syncthreads();
-    }
-    __syncthreads();
-  }
-}
-
 // B3, whole units: a unit of at most PER * kThreads records is loaded into registers, counted,
 // placed in LDS in sub-bucket order and written out once, so each (unit, partition) run leaves as
-// one stream of ~H / 2^s records (the round-based kernel above wrote it in ~H / SUB pieces, each
-// a partial line the L2 had to merge).
+// one stream of ~H / 2^s records (written in rounds of part of a unit, each run left as several
+// partial lines the L2 had to merge).
 template <bool HASHED, int PER>
 __global__ void __launch_bounds__(kThreads) freq_phaseB_scatter_u(BArgs a) {
   constexpr int W = FM<HASHED>::kRB / 8;
@@ -2863,101 +2566,6 @@ __global__ void __launch_bounds__(256) freq_cap_layout(const unsigned long long*
     part_end[p] = v;
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) part_base[P] = bbase[kBuckets];
-}
-
-// B3, whole units, persistent: workgroup g of an XCD takes that XCD's units g, g + G/8, ... and
-// issues the loads of its next unit right after placing the current one in LDS, so they are in
-// flight while the current unit's runs are written (freq_phaseB_scatter_u, one workgroup per CU by
-// LDS and one unit per workgroup, left every load latency exposed).  Same output.
-template <bool HASHED, int PER>
-__global__ void __launch_bounds__(kThreads) freq_phaseB_scatter_p(BArgs a) {
-  constexpr int W = FM<HASHED>::kRB / 8;
-  constexpr int SMAX = 1 << kMaxSubBits;
-  constexpr uint32_t NR = (uint32_t)PER * kThreads;
-  __shared__ UnitLds L;
-  __shared__ unsigned long long gbs[SMAX];
-  __shared__ uint32_t hcnt[SMAX];
-  __shared__ uint64_t staged[NR * W];
-  const uint32_t g = blockIdx.x, per_xcd = gridDim.x / 8u, q = (a.n_units + 7) / 8;
-  const uint32_t x = g & 7u, gl = g >> 3;
-  const uint32_t uend = min((x + 1) * q, a.n_units);
-  uint32_t w = x * q + gl;
-  if (w >= uend) return;  // (workgroup-uniform)
-  const int S = 1 << a.s;
-  const int tid = threadIdx.x;
-  for (int i = tid; i < S; i += kThreads) hcnt[i] = 0;
-  uint64_t rv[PER][W];
-  // the unit's records into rv (the loads are left in flight); returns its record count
-  auto load_unit = [&](uint32_t u) -> uint32_t {
-    unit_range(a, u, L);
-    const uint32_t nrec = L.s_hi - L.s_lo;  // <= NR (the host sizes units so)
-    uint32_t done = 0;
-    for (int64_t cw = L.s_c0; cw < L.s_c1; cw += kThreads) {  // windows of segments (usually one)
-      uint32_t nwin;
-      const uint32_t wtot = unit_window(a, L, cw, nwin);
-#pragma unroll
-      for (int j = 0; j < PER; ++j) {
-        const uint32_t r = (uint32_t)j * kThreads + tid;
-        if (r >= done && r < done + wtot) {
-          const uint64_t* src = reinterpret_cast<const uint64_t*>(a.recs) + window_rec(L, nwin, r - done) * W;
-#pragma unroll
-          for (int y = 0; y < W; ++y) rv[j][y] = src[y];
-        }
-      }
-      done += wtot;
-      __syncthreads();
-    }
-    return nrec;
-  };
-  uint32_t nrec = load_unit(w), b = L.s_b;
-  uint64_t* out = reinterpret_cast<uint64_t*>(a.recsB);
-  while (true) {
-    uint32_t lpos[PER];
-#pragma unroll
-    for (int j = 0; j < PER; ++j)
-      if ((uint32_t)j * kThreads + tid < nrec) lpos[j] = atomicAdd(&hcnt[rec_sub(rv[j], a.s, HASHED)], 1u);
-    __syncthreads();
-    const uint32_t cnt = tid < S ? hcnt[tid] : 0u;
-    uint32_t tot;
-    const uint32_t ex = block_excl_scan(cnt, L.s_wave, tot);  // (barriers: every count is read)
-    if (tid < S) {
-      hcnt[tid] = ex;
-      gbs[tid] = a.part_base[(uint64_t)b * S + tid] + a.uhist[(int64_t)w * S + tid];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-      if ((uint32_t)j * kThreads + tid >= nrec) continue;
-      const uint32_t slot = hcnt[rec_sub(rv[j], a.s, HASHED)] + lpos[j];
-#pragma unroll
-      for (int y = 0; y < W; ++y) staged[slot * W + y] = rv[j][y];
-    }
-    __syncthreads();
-    // the next unit's loads go out before this unit's stores
-    const uint32_t wn = w + per_xcd;
-    const bool more = wn < uend;
-    uint32_t nrec_n = 0, b_n = 0;
-    if (more) {
-      nrec_n = load_unit(wn);
-      b_n = L.s_b;
-    }
-    for (uint32_t i = tid; i < nrec; i += kThreads) {
-      uint64_t r[W];
-#pragma unroll
-      for (int y = 0; y < W; ++y) r[y] = staged[i * W + y];
-      const uint32_t sb = rec_sub(r, a.s, HASHED);
-      const unsigned long long d = gbs[sb] + (i - hcnt[sb]);
-#pragma unroll
-      for (int y = 0; y < W; ++y) out[d * W + y] = r[y];
-    }
-    if (!more) break;
-    __syncthreads();
-    for (int i = tid; i < S; i += kThreads) hcnt[i] = 0;
-    __syncthreads();
-    w = wn;
-    nrec = nrec_n;
-    b = b_n;
-  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3152,13 +2760,16 @@ DQ_DEV void store_fix(unsigned long long* p, fix128 v) {
   p[1] = (uint64_t)(v >> 64);
 }
 
-// Per work item: the inserts, then ONE pass over the LDS table that reads every slot once for
+// Hashed tables' recount rounds (a hashed first pass is freq_phaseC_h, exact tables run
+// freq_phaseC_x).  Per work item: the inserts, then ONE pass over the LDS table that reads every slot once for
 // the statistics, the Histogram candidates (kept in registers) and the lit probe, and clears it
 // for the next item (when the groups are materialised, the output pass clears instead).  The
 // flags and the special cell the inserts update are double-buffered by item parity, so they are
 // reset for item i + 1 while item i runs, between two of its barriers: three barriers per item.
+// (only the hashed instantiation is left; its text is kept as it was, so its code is too)
 template <bool HASHED>
 __global__ void __launch_bounds__(kCThreads, 4) freq_phaseC(CArgs a) {
+  static_assert(HASHED, "exact tables run freq_phaseC_x");
   using M = FM<HASHED>;
   constexpr int KT = M::kTableC, W = M::kRB / 8, NW = kCThreads / 64;
   __shared__ uint64_t tkey[KT], tcnt[KT];
@@ -3530,7 +3141,7 @@ __global__ void __launch_bounds__(kCThreads, 4) freq_phaseC(CArgs a) {
 // ------------------------------------------------------------------------------------------------
 // Phase C, exact mode (one fixed-width key: the hash is the key, no arena, no representative).
 //
-// The generic kernel above spends most of its issue slots on per-partition work that does not
+// freq_phaseC's form (above) spends most of its issue slots on per-partition work that does not
 // depend on the records: a pass over all kTableC slots (empty ones included), a 4-deep candidate
 // insertion per occupied slot, three barriers.  Here every claim appends its slot to an LDS list
 // (one LDS atomic per wave and insert round), so the statistics pass visits the partition's groups
@@ -3549,7 +3160,7 @@ __global__ void __launch_bounds__(kCThreads, 4) freq_phaseC(CArgs a) {
 // Only when a partition's largest count exceeds 1 AND Histogram wants candidates do kCand more
 // rounds (with barriers) pick its exact top kCand; a mostly-unique key never takes them.
 // Entropy stays deterministic: count-1 groups are counted, counts < kSmallCounts histogrammed, and
-// the partials are added in a fixed order.  Same outputs as freq_phaseC<false>.
+// the partials are added in a fixed order.
 // DBG: DQ_FREQ_DEBUG=2's instantiation, workgroup 0 stamps each item's phases (wall clock).
 // ------------------------------------------------------------------------------------------------
 // PK: packed slots, for tables partitioned at least kMinPkSubBits deep (a partition then fixes the
@@ -3794,10 +3405,7 @@ __global__ void __launch_bounds__(kCThreadsX<PK && BIG>, 4) freq_phaseC_x(CArgs 
 #pragma unroll
       for (int q = 0; q < PF; ++q) step[q] = ((uint32_t)(h[q] >> (PK ? 30 : 40)) | 1u) & (KT - 1);
       uint32_t mine = 0;
-#if DQ_C_EXPERIMENT & 2  // (timing experiment only: no inserts)
-      todo = 0;
-#endif
-      if constexpr (PK && DQ_LEAN_PROBE) {
+      if constexpr (PK) {
         // One CAS instruction per probe round: each lane works on its next pending record, so a
         // round is a full-width LDS atomic while the wave's records last, instead of PF
         // instructions whose lanes thin out to the longest probe sequence.  The CAS instructions,
@@ -3840,7 +3448,7 @@ __global__ void __launch_bounds__(kCThreadsX<PK && BIG>, 4) freq_phaseC_x(CArgs 
         mine = (1u << ncl) - 1u;
 #pragma unroll
         for (int x = 0; x < PF; ++x) slot[x] = cl[x];
-      } else {  // (PF records per lane in flight together; -DDQ_LEAN_PROBE=0: also for PK)
+      } else {  // (PF records per lane in flight together)
         // (a branch-light form of these rounds -- outcomes as bit masks, slots advanced with
         // selects -- measured no faster, profiles/r6g, and spilled the two-word kernel)
         for (int pr = 0; todo && pr < KT; ++pr) {
@@ -3851,13 +3459,9 @@ __global__ void __launch_bounds__(kCThreadsX<PK && BIG>, 4) freq_phaseC_x(CArgs 
           for (int q = 0; q < PF; ++q) {
             if (!((todo >> q) & 1u)) continue;
             const bool claimed = old[q] == kEmptyKey;
-            const bool match = PK ? ((old[q] ^ h[q]) & MK) == 0 : old[q] == h[q];
+            const bool match = old[q] == h[q];
             if (claimed || match) {
-              if constexpr (PK) {
-                if (!claimed) atomicAdd((unsigned long long*)&tkey[slot[q]], (unsigned long long)(c[q] << KB));
-              } else {
-                atomicAdd((unsigned long long*)&tcnt[slot[q]], (unsigned long long)c[q]);
-              }
+              atomicAdd((unsigned long long*)&tcnt[slot[q]], (unsigned long long)c[q]);
               if (claimed) mine |= 1u << q;
               todo &= ~(1u << q);
             } else {
@@ -3972,9 +3576,6 @@ __global__ void __launch_bounds__(kCThreadsX<PK && BIG>, 4) freq_phaseC_x(CArgs 
     // k: the key, or (PK) the packed slot word, rebuilt by key_of
     auto key_of = [&](uint64_t k) -> uint64_t { return PK ? (((uint64_t)p << KB) | (k & MK)) : k; };
     auto stat = [&](uint32_t i, uint64_t k, uint64_t c) {
-#if DQ_C_EXPERIMENT & 1  // (timing experiment only: no statistics)
-      return;
-#endif
       if (keep) a.groups[obase + i] = Group{key_of(k), c, 0};
       if (c == 1) {
         ++un;
@@ -4154,7 +3755,7 @@ __global__ void __launch_bounds__(kCThreadsX<PK && BIG>, 4) freq_phaseC_x(CArgs 
 // stores right after its CAS, so no barrier and no spin.  Equal hashes are decided on the arena
 // bytes (enc_equal_arena): a 64-bit collision stays two groups.  A partition this kernel cannot
 // take exactly (a record count >= 2^12, more than kCL records, the key kEmptyKey, a full table)
-// is handed on whole (an ovf entry, f = 0) to freq_phaseC<true>.
+// is handed on whole (an ovf entry, f = 0) to freq_phaseC.
 // ------------------------------------------------------------------------------------------------
 // enc_equal_arena with a rolled loop of 4-word rounds (few registers: it sits inside every probe
 // round of freq_phaseC_h); 4 words past a key's end stay inside the arena's 64-byte tail.
@@ -4561,7 +4162,7 @@ __global__ void __launch_bounds__(kCThreads, 4) freq_phaseC_h(CArgs a) {
     __syncthreads();  //                                                            [barrier 2]
     mark(2);
     if (overflow) {
-      if (tid == 0) {  // the whole partition, again, by the generic kernel
+      if (tid == 0) {  // the whole partition, again, by freq_phaseC
         const unsigned int q = atomicAdd(a.ovf_n, 1u);
         a.ovf_out[q] = FEntry{p, 0, 0, 0};
       }
@@ -5063,10 +4664,6 @@ static hipError_t grow_keep(DevBuf<T>& b, size_t used, size_t need, hipStream_t 
   DevBuf<T> nb;
   hipError_t e = nb.ensure(std::max(need, b.n * 2));
   if (e != hipSuccess) return e;
-#if DQ_A_NOCOPY  // (timing build: the never-written arena reads as zero words, so every key is 4 bytes)
-  e = hipMemsetAsync(nb.p, 0, nb.n * sizeof(T), st);
-  if (e != hipSuccess) return e;
-#endif
   if (used) {
     e = hipMemcpyAsync(nb.p, b.p, used * sizeof(T), hipMemcpyDeviceToDevice, st);
     if (e != hipSuccess) return e;
@@ -5137,17 +4734,17 @@ static void launch_phaseA(dq_freq* f, AArgs a, bool from_rec) {
   else
     clk = nullptr;
   a.dbg_clock = clk;
+  if constexpr (HASHED) {  // (exact rows: launch_pieces)
+    if (!from_rec && a.ks.n_keys == 1 && a.ks.cols[0].type == DQ_UTF8)
+      hipLaunchKernelGGL((freq_phaseA<true, false, true>), dim3((unsigned)n_wg),
+                         dim3(AKeys<true, false>::kThreads), 0, f->stream, a);
+    else if (!from_rec)
+      hipLaunchKernelGGL((freq_phaseA<true, false>), dim3((unsigned)n_wg),
+                         dim3(AKeys<true, false>::kThreads), 0, f->stream, a);
+  }
   if (from_rec)
     hipLaunchKernelGGL((freq_phaseA<HASHED, true>), dim3((unsigned)n_wg),
                        dim3(AKeys<HASHED, true>::kThreads), 0,
-                       f->stream, a);
-  else if (HASHED && a.ks.n_keys == 1 && a.ks.cols[0].type == DQ_UTF8)
-    hipLaunchKernelGGL((freq_phaseA<HASHED, false, HASHED>), dim3((unsigned)n_wg),
-                       dim3(AKeys<HASHED, false>::kThreads), 0,
-                       f->stream, a);
-  else
-    hipLaunchKernelGGL((freq_phaseA<HASHED, false>), dim3((unsigned)n_wg),
-                       dim3(AKeys<HASHED, false>::kThreads), 0,
                        f->stream, a);
   if (clk) {  // per-tile phase times of workgroup 0, us (the wall clock ticks at 100 MHz)
     unsigned long long h[16 * 8];
@@ -5173,11 +4770,7 @@ static void launch_phaseA(dq_freq* f, AArgs a, bool from_rec) {
 // returns at once when this one took the batch).  Tried while the batch's strings average at most
 // 8 bytes (its data_bytes hint) and until the table sees it give a batch up.
 static bool small_keys_worth_trying(dq_freq* f, const dq_column& k, int64_t rows) {
-  static const bool enabled = [] {
-    const char* e = getenv("DQ_FREQ_SMALL");
-    return !e || atoi(e) != 0;
-  }();
-  if (!enabled || f->exact || f->n_keys != 1 || f->types[0] != DQ_UTF8 || rows < 4096) return false;
+  if (f->exact || f->n_keys != 1 || f->types[0] != DQ_UTF8 || rows < 4096) return false;
   if (f->fast_off) return false;
   if (f->fast_seen.p && f->fast_epoch && *(volatile unsigned long long*)f->fast_seen.p == f->fast_epoch) {
     f->fast_off = true;  // the last attempt gave its batch up: long strings or many keys
@@ -5200,11 +4793,7 @@ static dq_status launch_phaseA_small(dq_freq* f, AArgs& a) {
   a.batch_tab = f->batch_tab.p;
   a.fast_epoch = ++f->fast_epoch;
   const KeyCol& c = a.ks.cols[0];
-  static const int poll = [] {  // DQ_FREQ_POLL: A/B hook for the give-up poll interval
-    const char* e = getenv("DQ_FREQ_POLL");
-    return e ? atoi(e) : 0;
-  }();
-  a.fast_poll = poll;
+  a.fast_poll = 0;
   a.vec_ok = (reinterpret_cast<uintptr_t>(c.values) & 15u) == 0 &&
              (reinterpret_cast<uintptr_t>(c.valid) & 3u) == 0;
   static const int cus = [] {
@@ -5253,15 +4842,6 @@ static bool xfixed_enabled() {
 static bool hpieces_enabled() {
   const char* e = getenv("DQ_FREQ_HPIECES");  // (read per batch: A/B in one process)
   return !e || atoi(e) != 0;
-}
-
-// Exact rows written bucket-major per batch (DQ_FREQ_PIECES=0: the per-tile chunk layout).
-static bool pieces_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("DQ_FREQ_PIECES");
-    return !e || atoi(e) != 0;
-  }();
-  return on;
 }
 
 // Pre-pass (rows per workgroup and bucket), its scan, and phase A into bucket pieces; the batch's
@@ -5313,33 +4893,18 @@ static dq_status launch_pieces(dq_freq* f, AArgs a, int64_t chunks) {
   a.ptot = f->ptot.p;
   a.pstart = f->pstart.p + (size_t)f->n_prow * kBuckets;
   a.plen = f->plen.p + (size_t)f->n_prow * kBuckets;
-  static const bool generic = [] {  // DQ_FREQ_GENERIC_A=1: A/B hook, the generic kernel
-    const char* e = getenv("DQ_FREQ_GENERIC_A");
-    return e && atoi(e) != 0;
-  }();
-  if (generic) {
-    if (a.zero_rows)  // (the generic kernel does not zero them)
-      HIP_TRY(hipMemsetAsync(a.hist + (size_t)a.zero_off * kHistRow, 0,
-                             (size_t)a.zero_rows * kHistRow * sizeof(uint16_t), f->stream));
-    a.zero_rows = 0;
-    f->nan_counted = false;
-    a.piece_cap = 0;  // (the generic kernel lays pieces out by the pre-pass)
-    launch_phaseA<false>(f, a, false);
-  } else {
-    static_assert(kAXThreads == kBuckets, "one bucket per thread");
-    a.dbg_clock = nullptr;
-    auto go = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3((unsigned)n_wg), dim3(kAXThreads), 0, f->stream, a);
-    };
-    switch (a.ks.cols[0].type) {  // one kernel per width (one kernel for all spilled heavily)
-      case DQ_INT8: go(freq_phaseA_xp<DQ_INT8>); break;
-      case DQ_INT16: go(freq_phaseA_xp<DQ_INT16>); break;
-      case DQ_INT32: go(freq_phaseA_xp<DQ_INT32>); break;
-      case DQ_FLOAT32: go(freq_phaseA_xp<DQ_FLOAT32>); break;
-      case DQ_FLOAT64: go(freq_phaseA_xp<DQ_FLOAT64>); break;
-      case DQ_BOOL: go(freq_phaseA_xp<DQ_BOOL>); break;
-      default: go(freq_phaseA_xp<DQ_INT64>); break;
-    }
+  static_assert(kAXThreads == kBuckets, "one bucket per thread");
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)n_wg), dim3(kAXThreads), 0, f->stream, a);
+  };
+  switch (a.ks.cols[0].type) {  // one kernel per width (one kernel for all spilled heavily)
+    case DQ_INT8: go(freq_phaseA_xp<DQ_INT8>); break;
+    case DQ_INT16: go(freq_phaseA_xp<DQ_INT16>); break;
+    case DQ_INT32: go(freq_phaseA_xp<DQ_INT32>); break;
+    case DQ_FLOAT32: go(freq_phaseA_xp<DQ_FLOAT32>); break;
+    case DQ_FLOAT64: go(freq_phaseA_xp<DQ_FLOAT64>); break;
+    case DQ_BOOL: go(freq_phaseA_xp<DQ_BOOL>); break;
+    default: go(freq_phaseA_xp<DQ_INT64>); break;
   }
   HIP_TRY(hipGetLastError());
   const unsigned long long base = (unsigned long long)f->n_chunks * f->tile;
@@ -5448,27 +5013,20 @@ static dq_status finalize_b(dq_freq* f) {
   // test hook: a small target forces deep partitioning (all s) on small inputs, a huge one the
   // recount path of overflowing partitions
   if (const char* e = getenv("DQ_FREQ_PARTITION_TARGET")) target = std::max(1, atoi(e));
-  if (const char* e = getenv("DQ_FREQ_PARTITION_TARGET_H"))  // (A/B: hashed tables only)
-    if (!f->exact) target = std::max(1, atoi(e));
   int s = 0;
   while (s < kMaxSubBits && ((uint64_t)kBuckets << s) * (uint64_t)target < R) ++s;
   // exact tables: one level shallower when the partitions stay packed (pk_ok: s >= kMinPkSubBits,
   // record counts within the count field) and hold <= kTargetPk records on average -- packed
   // slots take up to 4096 -- so phase C's per-item costs cover twice the records (configs[2]
   // 24.75 -> 24.2 ms); a shallower table would fall to the two-word slots (configs[4] +29 ms)
-  static const uint64_t kTargetPk = [] {  // DQ_FREQ_TARGET_PK: A/B hook (0: no shallower step)
-    const char* e = getenv("DQ_FREQ_TARGET_PK");
-    return e ? (uint64_t)std::max(0, atoi(e)) : (uint64_t)3700;
-  }();
-  if (f->exact && !getenv("DQ_FREQ_PARTITION_TARGET") && kTargetPk)
-    while (s - 1 >= kMinPkSubBits && ((uint64_t)kBuckets << (s - 1)) * kTargetPk >= R &&
+  if (f->exact && !getenv("DQ_FREQ_PARTITION_TARGET"))
+    while (s - 1 >= kMinPkSubBits && ((uint64_t)kBuckets << (s - 1)) * FM<false>::kTargetPk >= R &&
            f->h_counters[C_MAXCNT] < (1ULL << (s - 1 - 3)))
       --s;
-  static const int unit_tiles = [] {  // DQ_FREQ_UNIT_TILES: A/B hook for the phase-B unit size
-    const char* e = getenv("DQ_FREQ_UNIT_TILES");
-    return e ? std::max(1, atoi(e)) : 0;
-  }();
-  const uint64_t H = (uint64_t)f->tile * (unit_tiles ? unit_tiles : f->exact ? kUnitTilesX : kUnitTilesH);
+  // (a whole unit is staged by freq_phaseB_scatter_u: 8 records per thread exact, 4 hashed)
+  static_assert(FM<false>::kTile * kUnitTilesX <= 8 * kThreads, "an exact unit is staged whole");
+  static_assert(FM<true>::kTile * kUnitTilesH <= 4 * kThreads, "a hashed unit is staged whole");
+  const uint64_t H = (uint64_t)f->tile * (f->exact ? kUnitTilesX : kUnitTilesH);
   uint32_t u = 0;
   for (int b = 0; b < kBuckets; ++b) {
     f->h_unit_start[b] = u;
@@ -5534,30 +5092,15 @@ static dq_status finalize_b(dq_freq* f) {
   a.part_base = f->part_base.p;
   a.recsB = f->recsB.p;
   const unsigned grid = (u + 7) / 8 * 8;
-  constexpr uint64_t kUnitX = 16 * kThreads, kUnitH = 4 * kThreads;  // whole-unit capacities
-  static const int bsub = [] {  // DQ_FREQ_BSUB: A/B hook for the phase-B3 round size (0: whole units)
-    const char* e = getenv("DQ_FREQ_BSUB");
-    return e ? atoi(e) : 0;
-  }();
-  // one unit per workgroup (measured faster than the persistent form: exact, configs[2] 5.08 vs
+  // one unit per workgroup (measured faster than a persistent form: exact, configs[2] 5.08 vs
   // 5.61 ms; hashed, configs[4] 678 vs 826 us per launch once the segment window shares the
-  // staging LDS and two workgroups fit a CU).  DQ_FREQ_B3U=1 / DQ_FREQ_B3P=1: A/B hooks
-  static const int b3_env = [] {
-    const char* e = getenv("DQ_FREQ_B3U");
-    const char* p = getenv("DQ_FREQ_B3P");
-    return e && atoi(e) ? 1 : (p && atoi(p) ? 2 : 0);
-  }();
-  const bool b3u = b3_env != 2;
+  // staging LDS and two workgroups fit a CU)
   // Exact tables: the capacity layout, no count pass.  Every partition of bucket b gets room for
   // mean + 8 sqrt(mean) + 32 records (a bijective hash spreads distinct keys uniformly: the
   // overflow odds per partition are ~1e-15), the units' runs are placed by device-scope cursor
   // adds, and a table whose runs overflow anyway (heavy keys whose records all land in one
   // partition) is scattered again by the counted path below, and counts from then on.
-  static const bool no_capb = [] {  // DQ_FREQ_CAPB=0: A/B hook, always the counted layout
-    const char* e = getenv("DQ_FREQ_CAPB");
-    return e && atoi(e) == 0;
-  }();
-  if (f->exact && !no_capb && !f->cap_failed && bsub == 0 && b3u && H <= kUnitX / 2) {
+  if (f->exact && !f->cap_failed) {
     std::vector<unsigned long long>& w = f->h_cap_words;
     w.assign(2 * kBuckets + 1, 0ULL);
     // test hook (read per finalize): DQ_FREQ_CAP_SCALE < 1 shrinks the room so runs overflow
@@ -5597,19 +5140,11 @@ static dq_status finalize_b(dq_freq* f) {
     f->cap_failed = true;  // the counted layout, now and for this table's next finalizes
     a.cap_mode = 0;
   }
-  static const bool count_w = [] {  // DQ_FREQ_BCOUNT_WAVE=0: A/B hook, a workgroup per unit
-    const char* e = getenv("DQ_FREQ_BCOUNT_WAVE");
-    return !(e && atoi(e) == 0);
-  }();
   const unsigned ugrid = (unsigned)((u + kBcWaves - 1) / kBcWaves);
-  if (count_w && f->exact)
+  if (f->exact)
     hipLaunchKernelGGL(freq_phaseB_count_w<false>, dim3(ugrid), dim3(kBcWaves * 64), 0, f->stream, a);
-  else if (count_w)
-    hipLaunchKernelGGL(freq_phaseB_count_w<true>, dim3(ugrid), dim3(kBcWaves * 64), 0, f->stream, a);
-  else if (f->exact)
-    hipLaunchKernelGGL(freq_phaseB_count<false>, dim3(u), dim3(kThreads), 0, f->stream, a);
   else
-    hipLaunchKernelGGL(freq_phaseB_count<true>, dim3(u), dim3(kThreads), 0, f->stream, a);
+    hipLaunchKernelGGL(freq_phaseB_count_w<true>, dim3(ugrid), dim3(kBcWaves * 64), 0, f->stream, a);
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(freq_phaseB_scan, dim3(kBuckets), dim3(kThreads), 0, f->stream, a);
   HIP_TRY(hipGetLastError());
@@ -5625,30 +5160,10 @@ static dq_status finalize_b(dq_freq* f) {
                        f->part_base.p, P, f->scan_tmp.p);
   }
   HIP_TRY(hipGetLastError());
-  int cus = 256;
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, f->device);
-  const unsigned pgrid = (unsigned)std::max(8, cus / 8 * 8);  // one per CU (LDS), XCD multiple
-  if (bsub == 0 && f->exact && H <= kUnitX && !b3u) {
-    hipLaunchKernelGGL((freq_phaseB_scatter_p<false, 16>), dim3(pgrid), dim3(kThreads), 0, f->stream, a);
-  } else if (bsub == 0 && !f->exact && H <= kUnitH && !b3u) {
-    hipLaunchKernelGGL((freq_phaseB_scatter_p<true, 4>), dim3(pgrid), dim3(kThreads), 0, f->stream, a);
-  } else if (bsub == 0 && f->exact && H <= kUnitX / 2) {  // (64 KB staged: two workgroups per CU)
+  if (f->exact)  // (64 KB staged: two workgroups per CU)
     hipLaunchKernelGGL((freq_phaseB_scatter_u<false, 8>), dim3(grid), dim3(kThreads), 0, f->stream, a);
-  } else if (bsub == 0 && f->exact && H <= kUnitX) {
-    hipLaunchKernelGGL((freq_phaseB_scatter_u<false, 16>), dim3(grid), dim3(kThreads), 0, f->stream, a);
-  } else if (bsub == 0 && !f->exact && H <= kUnitH) {
+  else
     hipLaunchKernelGGL((freq_phaseB_scatter_u<true, 4>), dim3(grid), dim3(kThreads), 0, f->stream, a);
-  } else if (f->exact) {
-    if (bsub == 8192)
-      hipLaunchKernelGGL((freq_phaseB_scatter<false, 8192>), dim3(grid), dim3(kThreads), 0, f->stream, a);
-    else
-      hipLaunchKernelGGL((freq_phaseB_scatter<false, 4096>), dim3(grid), dim3(kThreads), 0, f->stream, a);
-  } else {
-    if (bsub == 8192)
-      hipLaunchKernelGGL((freq_phaseB_scatter<true, 8192>), dim3(grid), dim3(kThreads), 0, f->stream, a);
-    else
-      hipLaunchKernelGGL((freq_phaseB_scatter<true, 4096>), dim3(grid), dim3(kThreads), 0, f->stream, a);
-  }
   HIP_TRY(hipGetLastError());
   f->b_valid = true;
   return DQ_OK;
@@ -5730,16 +5245,8 @@ static dq_status finalize_c(dq_freq* f, bool want_groups, bool want_cand) {
     }
     HIP_TRY(f->ovf_a.ensure(2 * P));
     HIP_TRY(hipMemsetAsync(f->ovf_n.p, 0, 4, f->stream));
-    static const bool no_bcache = [] {  // DQ_FREQ_CBCACHE=0: A/B hook, scalar bounds per item
-      const char* e = getenv("DQ_FREQ_CBCACHE");
-      return e && atoi(e) == 0;
-    }();
-    a.bcache = !no_bcache && f->Rcap < (1ULL << 32) ? 1u : 0u;
-    static const bool no_contig = [] {  // DQ_FREQ_CCONTIG=0: A/B hook, strided phase-C items
-      const char* e = getenv("DQ_FREQ_CCONTIG");
-      return e && atoi(e) == 0;
-    }();
-    a.contig = no_contig ? 0u : 1u;
+    a.bcache = f->Rcap < (1ULL << 32) ? 1u : 0u;
+    a.contig = 1u;
     a.entries = nullptr;
     a.ovf_out = f->ovf_a.p;
     a.ovf_n = f->ovf_n.p;
@@ -5758,41 +5265,27 @@ static dq_status finalize_c(dq_freq* f, bool want_groups, bool want_cand) {
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, f->device);
     const unsigned persistent = (unsigned)std::max(1, cus * 2);
     unsigned grid = (unsigned)std::min<int64_t>(P, persistent);
-    static const bool old_c = [] {  // DQ_FREQ_OLDC=1: A/B hook, the generic exact kernel
-      const char* e = getenv("DQ_FREQ_OLDC");
-      return e && atoi(e) != 0;
-    }();
-    static const bool old_hc = [] {  // DQ_FREQ_OLDHC=1: A/B hook, the generic hashed kernel
-      const char* e = getenv("DQ_FREQ_OLDHC");
-      return e && atoi(e) != 0;
-    }();
-    static const bool no_pk = [] {  // DQ_FREQ_NOPK=1: A/B hook, no packed-slot first pass
-      const char* e = getenv("DQ_FREQ_NOPK");
-      return e && atoi(e) != 0;
-    }();
     for (int round = 0; round < 24; ++round) {
       // packed slots: the first pass of a table partitioned to the full depth (19 fixed bits)
-      const bool pk = round == 0 && pk_ok(f) && !no_pk;
+      const bool pk = round == 0 && pk_ok(f);
       // (packed, partitions of > 2048 records on average: one 1024-thread workgroup per CU)
       const bool big = pk && f->R > (uint64_t)P * 2048;
       const unsigned grid_pk = (unsigned)std::min<int64_t>(P, std::max(1, cus));
-      if (f->exact && !old_c && clk && pk && big)
+      if (f->exact && clk && pk && big)
         hipLaunchKernelGGL((freq_phaseC_x<true, true, true>), dim3(grid_pk), dim3(kCThreadsX<true>), 0, f->stream, a);
-      else if (f->exact && !old_c && clk && pk)
+      else if (f->exact && clk && pk)
         hipLaunchKernelGGL((freq_phaseC_x<true, true>), dim3(grid), dim3(kCThreads), 0, f->stream, a);
-      else if (f->exact && !old_c && clk)
+      else if (f->exact && clk)
         hipLaunchKernelGGL((freq_phaseC_x<true, false>), dim3(grid), dim3(kCThreads), 0, f->stream, a);
-      else if (f->exact && !old_c && pk && big)
+      else if (f->exact && pk && big)
         hipLaunchKernelGGL((freq_phaseC_x<false, true, true>), dim3(grid_pk), dim3(kCThreadsX<true>), 0, f->stream, a);
-      else if (f->exact && !old_c && pk)
+      else if (f->exact && pk)
         hipLaunchKernelGGL((freq_phaseC_x<false, true>), dim3(grid), dim3(kCThreads), 0, f->stream, a);
-      else if (f->exact && !old_c)
-        hipLaunchKernelGGL((freq_phaseC_x<false, false>), dim3(grid), dim3(kCThreads), 0, f->stream, a);
       else if (f->exact)
-        hipLaunchKernelGGL(freq_phaseC<false>, dim3(grid), dim3(kCThreads), 0, f->stream, a);
-      else if (round == 0 && !old_hc && clk)
+        hipLaunchKernelGGL((freq_phaseC_x<false, false>), dim3(grid), dim3(kCThreads), 0, f->stream, a);
+      else if (round == 0 && clk)
         hipLaunchKernelGGL(freq_phaseC_h<true>, dim3(grid), dim3(kCThreads), 0, f->stream, a);
-      else if (round == 0 && !old_hc)
+      else if (round == 0)
         hipLaunchKernelGGL(freq_phaseC_h<false>, dim3(grid), dim3(kCThreads), 0, f->stream, a);
       else
         hipLaunchKernelGGL(freq_phaseC<true>, dim3(grid), dim3(kCThreads), 0, f->stream, a);
@@ -5812,7 +5305,7 @@ static dq_status finalize_c(dq_freq* f, bool want_groups, bool want_cand) {
         HIP_TRY(d2h(&m, f->ovf_n.p, 4, f->stream));
       }
       if (m) reduced = false;
-      if (clk && ((f->exact && !old_c) || (!f->exact && round == 0 && !old_hc))) {  // C_x / C_h: 8 stamps per item
+      if (clk && (f->exact || round == 0)) {  // C_x / C_h: 8 stamps per item
         unsigned long long h[16 * 8];
         (void)hipMemcpy(h, clk, sizeof(h), hipMemcpyDeviceToHost);
         double acc[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -5833,7 +5326,7 @@ static dq_status finalize_c(dq_freq* f, bool want_groups, bool want_cand) {
                   acc[0] / ni, acc[1] / ni, acc[2] / ni, acc[3] / ni, acc[4] / ni, acc[5] / ni,
                   acc[6] / ni, ni);
         (void)hipMemset(clk, 0, sizeof(h));
-      } else if (clk) {  // per-item phase times of workgroup 0, us (the wall clock ticks at 100 MHz)
+      } else if (clk) {  // freq_phaseC (hashed recounts): workgroup 0's per-item phase times, us
         unsigned long long h[16 * 4];
         (void)hipMemcpy(h, clk, sizeof(h), hipMemcpyDeviceToHost);
         double acc[4] = {0, 0, 0, 0};
@@ -5847,10 +5340,9 @@ static dq_status finalize_c(dq_freq* f, bool want_groups, bool want_cand) {
           ++ni;
         }
         if (ni)
-          fprintf(stderr, "dq_freq phase C%s wg0 per item (us): inserts %.2f stats %.2f "
+          fprintf(stderr, "dq_freq phase C hashed wg0 per item (us): inserts %.2f stats %.2f "
                   "entropy+cand %.2f tail %.2f (%d items, grid %u, round %d)\n",
-                  f->exact ? " exact" : " hashed", acc[0] / ni, acc[1] / ni, acc[2] / ni,
-                  acc[3] / ni, ni, grid, round);
+                  acc[0] / ni, acc[1] / ni, acc[2] / ni, acc[3] / ni, ni, grid, round);
         (void)hipMemset(clk, 0, sizeof(h));
       }
       if (m == 0) break;
@@ -5861,9 +5353,7 @@ static dq_status finalize_c(dq_freq* f, bool want_groups, bool want_cand) {
       // recount the overflowing partitions over disjoint hash subsets
       // (a packed-slot first pass hands whole partitions on: no hash subsets yet)
       // (so does the hashed first pass)
-      if (!(round == 0 && pk_ok(f) && !no_pk && f->exact && !old_c) &&
-          !(round == 0 && !f->exact && !old_hc))
-        f->recounted = true;
+      if (!(round == 0 && (pk || !f->exact))) f->recounted = true;
       f->ovf_a.swap(f->ovf_b);  // ovf_b = this round's entries
       HIP_TRY(f->ovf_a.ensure(2 * (size_t)m));
       HIP_TRY(hipMemsetAsync(f->ovf_n.p, 0, 4, f->stream));
@@ -6732,7 +6222,7 @@ extern "C" dq_status dq_freq_create(int device, int n_keys, const int32_t* key_t
     // one utf8 key: + the fixed-capacity bucket pieces (1.5x the rows; dq_freq_add_device), and
     // their piece rows (growing any of them copies the table and waits for the stream)
     const bool hp = !f->exact && n_keys == 1 && f->types[0] == DQ_UTF8 && hpieces_enabled();
-    if (f->exact && pieces_enabled() && xfixed_enabled()) {  // + exact fixed-capacity pieces
+    if (f->exact && xfixed_enabled()) {  // + exact fixed-capacity pieces
       int64_t n_wg = 0;
       phaseA_chunks(false, false, capacity_hint, f->tile, &n_wg);
       n_wg += 2 * (capacity_hint >> 24) + 16;
@@ -6750,7 +6240,7 @@ extern "C" dq_status dq_freq_create(int device, int n_keys, const int32_t* key_t
     }
     dq_status st = ensure_chunks(f.get(), chunks);
     if (st != DQ_OK) return st;
-    if (f->exact && pieces_enabled()) {  // the pre-pass rows too: growing them waits for the stream
+    if (f->exact) {  // the pre-pass rows too: growing them waits for the stream
       int64_t n_wg = 0;
       phaseA_chunks(false, false, capacity_hint, f->tile, &n_wg);
       n_wg += 2 * (capacity_hint >> 24) + 16;
@@ -6832,11 +6322,10 @@ extern "C" dq_status dq_freq_add_device(dq_freq* f, const dq_column* keys, int n
   // batch's chunks (1.5x a workgroup's mean rows per bucket; a tile's records past a full piece
   // stay in its chunk), so phase B reads runs of ~60 records instead of ~4 per chunk
   const bool small = small_keys_worth_trying(f, keys[0], rows);
-  const bool xpieces = f->exact && pieces_enabled();
-  const bool dense = xpieces && dense_worth_trying(f, keys[0], rows);
+  const bool dense = f->exact && dense_worth_trying(f, keys[0], rows);
   int64_t hp_wg = 0, piece_chunks = 0;
   uint32_t hp_cap = 0;
-  if (xpieces && !dense && xfixed_enabled()) {
+  if (f->exact && !dense && xfixed_enabled()) {
     // exact rows into fixed-capacity pieces (1.25x a workgroup's mean rows per bucket; a tile's
     // records past a full piece stay in its chunk): no pre-pass over the keys
     phaseA_chunks(false, false, rows, f->tile, &hp_wg);
@@ -6919,7 +6408,7 @@ extern "C" dq_status dq_freq_add_device(dq_freq* f, const dq_column* keys, int n
     dq_status ss = launch_phaseA_small(f, a);
     if (ss != DQ_OK) return ss;
   }
-  if (xpieces) {
+  if (f->exact) {
     if (dense) {
       if (!f->dense_seen.p) {
         HIP_TRY(pinned_word_get(&f->dense_seen.p));
@@ -6935,9 +6424,6 @@ extern "C" dq_status dq_freq_add_device(dq_freq* f, const dq_column* keys, int n
     }
     dq_status ps = launch_pieces(f, a, chunks);  // (and the decline word's copy, when dense)
     if (ps != DQ_OK) return ps;
-  } else if (f->exact) {
-    f->nan_counted = false;
-    launch_phaseA<false>(f, a, false);
   } else {
     launch_phaseA<true>(f, a, false);
   }
