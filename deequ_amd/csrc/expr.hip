@@ -4,8 +4,6 @@
 // Analyzer.scala:385-408; Compliance.scala:37-53).
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "device_util.h"
 #include "kernels.h"
 #include "jfmt.h"
@@ -366,9 +364,10 @@ __global__ void __launch_bounds__(kBlock) expr_kernel(const XInstr* __restrict__
 // build_regex_table): one u8 successor per (state, byte) -- the byte classes folded in, terminal
 // states (sticky accept / dead) made self-loops -- then per state bit 0 = accepted after the
 // end-of-text symbol, bit 1 = terminal.  The block stages it in LDS with 16-byte copies, so a byte
-// costs one dependent LDS read.  A lane walks two rows (rows r and r + 64 of a 128-row pair of
-// bitmap words: two independent chains in flight), loading each string 16 bytes at a time with one
-// unaligned load; a row stops at its end or in a terminal state, the wave when every row has.
+// costs one dependent LDS read.  A lane walks four rows (rows r, r + 64, r + 128 and r + 192 of a
+// 256-row group of four bitmap words: four independent chains in flight), loading each string 16
+// bytes at a time with one unaligned load -- byte-wise and bounds-checked within 16 bytes of the
+// data buffer's end; a row stops at its end or in a terminal state, the wave when every row has.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint4 ldg128_unaligned(const uint8_t* p) {
   typedef unsigned int v4u __attribute__((ext_vector_type(4), aligned(1)));
@@ -483,20 +482,13 @@ hipError_t launch_regex(const uint8_t* valid, const int32_t* offsets, const uint
                         uint64_t* out_val, uint64_t* out_vld, hipStream_t stream) {
   if (rows <= 0) return hipSuccess;
   if (ns < 1 || ns > kRegexMaxStates) return hipErrorInvalidValue;
-  static const int hr = [] {  // DQ_RX_ROWS=2: A/B hook, two rows per lane
-    const char* e = getenv("DQ_RX_ROWS");
-    return e && atoi(e) == 2 ? 2 : 4;
-  }();
+  constexpr int hr = 4;  // rows per lane
   const int64_t groups = ((rows + 63) / 64 + hr - 1) / hr;
   int64_t blocks = (groups + 3) / 4;
   if (blocks > 8192) blocks = 8192;
   const size_t lds = ((size_t)ns * 257 + 15) / 16 * 16;
-  if (hr == 2)
-    hipLaunchKernelGGL(regex_find_kernel<2>, dim3((unsigned)blocks), dim3(kBlock), lds, stream, valid,
-                       offsets, data, rows, table, ns, start, null_mode, out_val, out_vld);
-  else
-    hipLaunchKernelGGL(regex_find_kernel<4>, dim3((unsigned)blocks), dim3(kBlock), lds, stream, valid,
-                       offsets, data, rows, table, ns, start, null_mode, out_val, out_vld);
+  hipLaunchKernelGGL(regex_find_kernel<hr>, dim3((unsigned)blocks), dim3(kBlock), lds, stream, valid,
+                     offsets, data, rows, table, ns, start, null_mode, out_val, out_vld);
   return hipGetLastError();
 }
 

@@ -203,7 +203,7 @@ def test_approx_quantile_small_relative_error_beyond_the_head_buffer(eps, gpu_de
 
 @pytest.mark.parametrize("name", ["URL", "EMAIL", "SOCIAL_SECURITY_NUMBER_US", "CREDITCARD"])
 def test_pattern_match_library_patterns_on_long_rows(name, gpu_device):
-    """The fused-table regex kernel (regex_find_kernel: 16-byte chunks, two rows per lane, early
+    """The fused-table regex kernel (regex_find_kernel: 16-byte chunks, four rows per lane, early
     stop in terminal states) on the reference's own patterns (PatternMatch.scala:56-72) over rows
     of 0..90 bytes that plant matches, near-misses and non-ASCII bytes at every chunk offset, the
     last rows ending at the data buffer's end (the bounds-checked chunk path); NULL rows count as
