@@ -57,6 +57,34 @@ DQ_DEV uint32_t ld32_slow(const uint8_t* bm, int64_t word, int64_t rows) {
 // ------------------------------------------------------------------------------------------------
 // TK_NUMERIC: n, wrapping Long sum, min/max in the column type, (n, avg, m2), fused predicates
 // ------------------------------------------------------------------------------------------------
+// Block means.  A lane's block is reduced in two passes: mb = s / nb, then the deviations x - mb.
+// The rounded mean can leave the block's [min, max] (0.1 + 0.1 + 0.1 already rounds): on a constant
+// block the deviations are then an ulp each instead of 0, and a constant column reports a non-zero
+// m2 and a Correlation where Spark has 0 and NaN (0 / 0).  The exact mean lies in [min, max], so
+// clamping the mean into it only moves it towards the exact one.  Finding min and max costs as much
+// as a pass, so it is done only where it can matter: if mb lies outside [min, max], every value is
+// within nb (nb + 1) 2^-53 max|x| < 2^-44 |mb| of mb (nb <= 16), hence m2b <= nb (2^-44 mb)^2.
+DQ_DEV bool near_constant(double m2b, int nb, double mb) {
+  return m2b <= (double)nb * (mb * mb) * 0x1p-88;  // false for a NaN mean or moment
+}
+
+// mb clamped into the [min, max] of the N values selected by sel; true if that moved it.
+template <int N, typename T>
+DQ_DEV bool clamp_block_mean(const T* x, uint32_t sel, double& mb) {
+  double lo = INFINITY, hi = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const bool on = (sel >> i) & 1u;
+    const double xd = (double)x[i];
+    lo = (on && xd < lo) ? xd : lo;
+    hi = (on && xd > hi) ? xd : hi;
+  }
+  const double c = mb < lo ? lo : (mb > hi ? hi : mb);
+  const bool moved = c != mb;
+  mb = c;
+  return moved;
+}
+
 struct NumLane {
   int64_t n = 0, si = 0, kmin = INT64_MAX, kmax = INT64_MIN;
   double sd = 0.0, mean = 0.0, m2 = 0.0;
@@ -118,12 +146,20 @@ DQ_DEV void num_vals(NumLane& L, const T* x, uint32_t vb, uint32_t wt, const Tas
       L.kmax = (on && k > L.kmax) ? k : L.kmax;
     }
     if constexpr (std::is_floating_point<T>::value) L.sd += s;
-    const double mb = s / (double)nb;
+    double mb = s / (double)nb;
     double m2b = 0.0;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const double d = (double)x[i] - mb;
       m2b += ((sel >> i) & 1u) ? d * d : 0.0;
+    }
+    if (near_constant(m2b, nb, mb) && clamp_block_mean<NV>(x, sel, mb)) {
+      m2b = 0.0;
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const double d = (double)x[i] - mb;
+        m2b += ((sel >> i) & 1u) ? d * d : 0.0;
+      }
     }
     if (L.n == 0) {
       L.mean = mb;
@@ -655,12 +691,20 @@ DQ_DEV void dec_item(const TaskDesc& t, int64_t r_begin, int64_t r_end, Acc& acc
     double sum = 0.0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) sum += x[k];
-    const double mb = sum / (double)nb;
+    double mb = sum / (double)nb;
     double m2b = 0.0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const double d = x[k] - mb;
       m2b += ((sel >> k) & 1u) ? d * d : 0.0;
+    }
+    if (near_constant(m2b, nb, mb) && clamp_block_mean<4>(x, sel, mb)) {
+      m2b = 0.0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const double d = x[k] - mb;
+        m2b += ((sel >> k) & 1u) ? d * d : 0.0;
+      }
     }
     if (n == 0) {
       mean = mb;
@@ -692,6 +736,25 @@ DQ_DEV void dec_item(const TaskDesc& t, int64_t r_begin, int64_t r_end, Acc& acc
 // (mean, co-moments), then one Chan merge -- 2 divisions per 16 rows instead of per 8.
 DQ_DEV double as_f64(uint64_t bits, bool is_long) {
   return is_long ? (double)(int64_t)bits : __builtin_bit_cast(double, bits);
+}
+
+// b = (xAvg, yAvg, ck, xMk, yMk) of one block of N rows: where a side is near constant, its mean
+// is clamped into the block's [min, max] and the three moments are taken again.
+template <int N>
+DQ_DEV void comoments_fix(const double* xs, const double* ys, uint32_t sel, int nb, double* b) {
+  const bool fx = near_constant(b[3], nb, b[0]) && clamp_block_mean<N>(xs, sel, b[0]);
+  const bool fy = near_constant(b[4], nb, b[1]) && clamp_block_mean<N>(ys, sel, b[1]);
+  if (!fx && !fy) return;
+  b[2] = b[3] = b[4] = 0.0;
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    if ((sel >> i) & 1u) {
+      const double dx = xs[i] - b[0], dy = ys[i] - b[1];
+      b[2] += dx * dy;
+      b[3] += dx * dx;
+      b[4] += dy * dy;
+    }
+  }
 }
 
 // The co-moments of a lane's 16 rows (bit i of sel: row i selected) merged into (n, c).
@@ -729,6 +792,7 @@ DQ_DEV void corr_fold16(const uint4* qx, const uint4* qy, uint32_t sel, bool xl,
       b[4] += dy * dy;
     }
   }
+  comoments_fix<2 * K>(xs, ys, sel, nb, b);
   if (n == 0) {
     for (int f = 0; f < 5; ++f) c[f] = b[f];
   } else {
@@ -833,6 +897,7 @@ DQ_DEV void corr_rows(const TaskDesc& t, int64_t r_begin, int64_t r_end, Acc& ac
         b[4] += dy * dy;
       }
     }
+    comoments_fix<8>(xs, ys, sel, nb, b);
     if (n == 0) {
       for (int f = 0; f < 5; ++f) c[f] = b[f];
     } else {

@@ -281,19 +281,7 @@ def test_hll_strings_of_every_length_match_oracle(n, batch, gpu_device):
         assert list(st.words) == O.agg_hll(ot, "s", w), w
 
 
-def _exact_moments(xs, ys):
-    """Population moments in exact rational arithmetic (fractions.Fraction over the float inputs):
-    the value both Spark's row-sequential update (Correlation.scala:37-52 merge, Corr update) and
-    the device's blocked two-pass + Chan merges approximate."""
-    from fractions import Fraction as F
-    n = len(xs)
-    fx, fy = [F(x) for x in xs], [F(y) for y in ys]
-    mx, my = sum(fx) / n, sum(fy) / n
-    dx, dy = [x - mx for x in fx], [y - my for y in fy]
-    return dict(n=n, mx=mx, my=my, ck=sum(a * b for a, b in zip(dx, dy)),
-                xm=sum(a * a for a in dx), ym=sum(b * b for b in dy),
-                sx=sum(abs(x) for x in fx) / n, sy=sum(abs(y) for y in fy) / n,
-                sck=sum(abs(a * b) for a, b in zip(dx, dy)))
+from moment_cases import exact_moments as _exact_moments  # noqa: E402  (moved; the name stays)
 
 
 @pytest.mark.parametrize("n,null_rate,batch,rho", [(4097, 0.05, None, 0.0), (20_011, 0.3, 4096, 0.0),

@@ -365,7 +365,8 @@ class _ArrowDeviceColumn:
 
         from deequ_amd import _native as N
         from deequ_amd.loader import ArrowArrayC, ArrowSchemaC
-        fmt = {pa.int64(): b"l", pa.int32(): b"i", pa.int16(): b"s", pa.int8(): b"c"}[arr.type]
+        fmt = {pa.int64(): b"l", pa.int32(): b"i", pa.int16(): b"s", pa.int8(): b"c", pa.float64(): b"g",
+               pa.float32(): b"f"}[arr.type]
         self.dev = [torch.from_numpy(np.frombuffer(b, np.uint8).copy()).to(device) for b in arr.buffers()]
         self.ptrs = (ctypes.c_void_p * 2)(self.dev[0].data_ptr(), self.dev[1].data_ptr())
         n = len(arr) - offset
