@@ -63,7 +63,10 @@ def type_name(t: int) -> str:
 # dq_xop
 (X_COL, X_NULL, X_BOOL, X_I64, X_F64, X_STR, X_IS_NULL, X_IS_NOT_NULL, X_NOT, X_AND, X_OR, X_EQ,
  X_NE, X_LT, X_LE, X_GT, X_GE, X_EQ_NULL_SAFE, X_IN, X_CAST_F64, X_REGEX, X_CAST_F32,
- X_DEC128) = range(1, 24)
+ X_DEC128, X_LIKE, X_ARITH, X_FUNC) = range(1, 27)
+# dq_arith_op / dq_func (the `which` word of X_ARITH / X_FUNC)
+AR_ADD, AR_SUB, AR_MUL, AR_DIV, AR_MOD, AR_NEG = range(1, 7)
+FN_ABS, FN_LENGTH, FN_COALESCE, FN_ISNAN = range(1, 5)
 
 # dq_agg_kind
 (AGG_COUNT_ALL, AGG_COUNT_NOTNULL, AGG_COUNT_TRUE, AGG_SUM, AGG_MIN, AGG_MAX, AGG_STDDEV_POP,

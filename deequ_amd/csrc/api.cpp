@@ -105,6 +105,7 @@ static int type_size(int t) {
 struct Node {
   int op = 0;
   int col = -1;
+  int rt = 0;  // DQ_X_ARITH / DQ_X_FUNC: the result's dq_type (i = which)
   int64_t i = 0;
   double d = 0.0;
   std::string s;
@@ -205,10 +206,93 @@ static bool parse_node(const int64_t* w, int n, int& pos, std::unique_ptr<Node>&
         if (!child()) return false;
       break;
     }
+    case DQ_X_LIKE: {
+      if (pos >= n) return false;
+      const int64_t nb = w[pos++];
+      const int64_t nw = (nb + 7) / 8;
+      if (nb < 0 || nb > DQ_LIKE_MAX_BYTES || pos + nw > n) return false;
+      node->s.assign(reinterpret_cast<const char*>(&w[pos]), (size_t)nb);
+      pos += (int)nw;
+      // validate the program's shape before any device code indexes it: known token kinds, literal
+      // lengths that stay inside it, no two ANYSEQ in a row (the host collapses them)
+      const uint8_t* pr = reinterpret_cast<const uint8_t*>(node->s.data());
+      int prev = 0;
+      for (int64_t k = 0; k < nb;) {
+        const int kind = pr[k];
+        if (kind == DQ_LIKE_LIT) {
+          if (k + 3 > nb) return false;
+          const int64_t len = pr[k + 1] | (pr[k + 2] << 8);
+          if (len < 1 || k + 3 + len > nb) return false;
+          k += 3 + len;
+        } else if (kind == DQ_LIKE_ANY1 || (kind == DQ_LIKE_ANYSEQ && prev != DQ_LIKE_ANYSEQ)) {
+          k += 1;
+        } else {
+          return false;
+        }
+        prev = kind;
+      }
+      if (!child()) return false;
+      break;
+    }
+    case DQ_X_ARITH: {
+      if (pos + 1 >= n) return false;
+      const int64_t which = w[pos++], rt = w[pos++];
+      if (which < DQ_AR_ADD || which > DQ_AR_NEG || rt < DQ_INT8 || rt > DQ_FLOAT64) return false;
+      if (which == DQ_AR_DIV && rt != DQ_FLOAT64) return false;  // always a double division
+      node->i = which;
+      node->rt = (int)rt;
+      if (!child() || (which != DQ_AR_NEG && !child())) return false;
+      break;
+    }
+    case DQ_X_FUNC: {
+      if (pos + 2 >= n) return false;
+      const int64_t which = w[pos++], rt = w[pos++], na = w[pos++];
+      bool ok = false;
+      switch (which) {
+        case DQ_FN_ABS: ok = na == 1 && rt >= DQ_INT8 && rt <= DQ_FLOAT64; break;
+        case DQ_FN_LENGTH: ok = na == 1 && rt == DQ_INT32; break;
+        case DQ_FN_COALESCE: ok = na >= 2 && na <= 8 && ((rt >= DQ_INT8 && rt <= DQ_FLOAT64) || rt == DQ_UTF8); break;
+        case DQ_FN_ISNAN: ok = na == 1 && rt == DQ_BOOL; break;
+        default: break;
+      }
+      if (!ok) return false;
+      node->i = which;
+      node->rt = (int)rt;
+      for (int64_t k = 0; k < na; ++k)
+        if (!child()) return false;
+      break;
+    }
     default: return false;
   }
   out = std::move(node);
   return true;
+}
+
+// The operators only the generic interpreter evaluates (LIKE, arithmetic, scalar functions): an
+// expression that holds one anywhere is materialised as an expression bitmap, never fused.
+static bool interpreter_only(const Node& n) {
+  if (n.op == DQ_X_LIKE || n.op == DQ_X_ARITH || n.op == DQ_X_FUNC) return true;
+  for (auto& k : n.kids)
+    if (interpreter_only(*k)) return true;
+  return false;
+}
+
+// The shape of a (validated) LIKE pattern program (kernels.h LikeShape).
+static int like_shape(const std::string& prog) {
+  std::vector<int> kinds;
+  for (size_t k = 0; k < prog.size();) {
+    const int kind = (uint8_t)prog[k];
+    kinds.push_back(kind);
+    k += kind == DQ_LIKE_LIT ? 3 + ((uint8_t)prog[k + 1] | ((uint8_t)prog[k + 2] << 8)) : 1;
+  }
+  const int L = DQ_LIKE_LIT, S = DQ_LIKE_ANYSEQ;
+  if (kinds.empty() || kinds == std::vector<int>{L}) return LK_EQ;
+  if (kinds == std::vector<int>{S}) return LK_ALL;
+  if (kinds == std::vector<int>{L, S}) return LK_PREFIX;
+  if (kinds == std::vector<int>{S, L}) return LK_SUFFIX;
+  if (kinds == std::vector<int>{S, L, S}) return LK_CONTAINS;
+  if (kinds == std::vector<int>{L, S, L}) return LK_ENDS;
+  return LK_GENERAL;
 }
 
 static bool is_cmp(int op) { return op >= DQ_X_EQ && op <= DQ_X_GE; }
@@ -263,6 +347,14 @@ static void compile_postfix(const Node& n, std::vector<XInstr>& prog, std::strin
       pool += n.s;
       break;
     }
+    case DQ_X_LIKE: {
+      while (pool.size() % 4) pool.push_back('\0');
+      ins = {XI_LIKE, (int32_t)n.s.size() | (like_shape(n.s) << 16), (int64_t)pool.size()};
+      pool += n.s;
+      break;
+    }
+    case DQ_X_ARITH: ins = {XI_ARITH, (int32_t)n.i | (n.rt << 8), 0}; break;
+    case DQ_X_FUNC: ins = {XI_FUNC, (int32_t)n.i | (n.rt << 8), (int64_t)n.kids.size()}; break;
     default: ins = {XI_CMP, n.op, 0}; break;
   }
   prog.push_back(ins);
@@ -376,6 +468,7 @@ static bool leaf_cmp(const Node& n, const std::vector<int32_t>& types, CmpLeaf& 
 // [col IS NULL OR] (cmp [AND cmp])  on one numeric column
 static bool fuse_numeric(const Node& n, const std::vector<int32_t>& types, int& col, NumPred& p) {
   p = NumPred{};
+  if (interpreter_only(n)) return false;
   const Node* body = &n;
   int null_col = -1;
   if (n.op == DQ_X_OR && n.kids[0]->op == DQ_X_IS_NULL && n.kids[0]->kids[0]->op == DQ_X_COL) {
@@ -449,6 +542,7 @@ static bool fuse_str_in_body(const Node& n, const std::vector<int32_t>& types, S
 
 static bool fuse_str_in(const Node& n, const std::vector<int32_t>& types, StrIn& s) {
   s = StrIn{};
+  if (interpreter_only(n)) return false;
   if (n.op == DQ_X_OR && n.kids[0]->op == DQ_X_IS_NULL && n.kids[0]->kids[0]->op == DQ_X_COL) {
     int nc = n.kids[0]->kids[0]->col;
     if (!fuse_str_in_body(*n.kids[1], types, s)) return false;
@@ -1090,7 +1184,8 @@ extern "C" dq_status dq_state_create(const dq_plan* plan, int device, dq_state**
   // pool offsets in the programs are relative to each expression's own pool
   for (size_t k = 0; k < plan->mat.size(); ++k)
     for (size_t q = 0; q < plan->mat[k].prog.size(); ++q)
-      if (prog[s->prog_off[k] + q].op == XI_STR || prog[s->prog_off[k] + q].op == XI_REGEX)
+      if (prog[s->prog_off[k] + q].op == XI_STR || prog[s->prog_off[k] + q].op == XI_REGEX ||
+          prog[s->prog_off[k] + q].op == XI_LIKE)
         prog[s->prog_off[k] + q].imm += s->pool_off[k];
   HIP_TRY(s->d_prog.ensure(std::max<size_t>(1, prog.size())));
   if (!prog.empty())

@@ -148,6 +148,206 @@ DQ_DEV bool parse_f64(const uint8_t* s, int32_t len, double& out) {
   return true;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Arithmetic and scalar functions (DQ_X_ARITH / DQ_X_FUNC): Spark 2.2 semantics in the result type
+// the host computed (numericPrecedence; Division: always double).  Operands are numbers by the
+// host's typing (tag 2 or 3; a boolean counts as its integer); anything else gives NULL.
+// ------------------------------------------------------------------------------------------------
+constexpr V kNullV{0, 0, 0, 0.0, nullptr};
+
+// an integral result at the width of its type: Java's wrap-around (a sign extension of the low bits)
+DQ_DEV int64_t wrap_int(int64_t v, int rt) {
+  switch (rt) {
+    case DQ_INT8: return (int8_t)v;
+    case DQ_INT16: return (int16_t)v;
+    case DQ_INT32: return (int32_t)v;
+    default: return v;
+  }
+}
+
+// a numeric value in the type `rt` (Spark's Cast to the common type; never narrows an integer)
+DQ_DEV V to_num_type(V a, int rt) {
+  if (a.tag == 0) return kNullV;
+  if (a.tag > 3) return kNullV;
+  if (rt == DQ_FLOAT32) {
+    const float f = a.tag == 3 ? (float)a.d : (float)a.i;  // (float)long: one rounding
+    return V{3, 1, 0, (double)f, nullptr};
+  }
+  if (rt == DQ_FLOAT64) return V{3, 0, 0, a.tag == 3 ? a.d : (double)a.i, nullptr};
+  return a.tag == 3 ? kNullV : V{2, 0, a.i, 0.0, nullptr};
+}
+
+DQ_DEV V arith_eval(const V& a, const V& b, int which, int rt) {
+  const bool unary = which == DQ_AR_NEG;
+  if (a.tag == 0 || a.tag > 3 || (!unary && (b.tag == 0 || b.tag > 3))) return kNullV;
+  if (rt == DQ_FLOAT32) {
+    const float x = a.tag == 3 ? (float)a.d : (float)a.i;
+    const float y = unary ? 0.0f : (b.tag == 3 ? (float)b.d : (float)b.i);
+    float r;
+    switch (which) {
+      case DQ_AR_ADD: r = x + y; break;
+      case DQ_AR_SUB: r = x - y; break;
+      case DQ_AR_MUL: r = x * y; break;
+      case DQ_AR_MOD:
+        if (y == 0.0f) return kNullV;
+        r = fmodf(x, y);
+        break;
+      case DQ_AR_NEG: r = -x; break;
+      default: return kNullV;  // (a division is always double: dq_plan_create)
+    }
+    return V{3, 1, 0, (double)r, nullptr};
+  }
+  if (rt == DQ_FLOAT64) {
+    const double x = a.tag == 3 ? a.d : (double)a.i;
+    const double y = unary ? 0.0 : (b.tag == 3 ? b.d : (double)b.i);
+    double r;
+    switch (which) {
+      case DQ_AR_ADD: r = x + y; break;
+      case DQ_AR_SUB: r = x - y; break;
+      case DQ_AR_MUL: r = x * y; break;
+      case DQ_AR_DIV:
+        if (y == 0.0) return kNullV;
+        r = x / y;
+        break;
+      case DQ_AR_MOD:
+        if (y == 0.0) return kNullV;
+        r = fmod(x, y);
+        break;
+      default: r = -x; break;
+    }
+    return V{3, 0, 0, r, nullptr};
+  }
+  if (a.tag == 3 || (!unary && b.tag == 3)) return kNullV;  // (an integral result of a double)
+  const uint64_t x = (uint64_t)a.i, y = unary ? 0 : (uint64_t)b.i;
+  uint64_t r;
+  switch (which) {
+    case DQ_AR_ADD: r = x + y; break;
+    case DQ_AR_SUB: r = x - y; break;
+    case DQ_AR_MUL: r = x * y; break;
+    case DQ_AR_MOD:
+      if (b.i == 0) return kNullV;
+      r = b.i == -1 ? 0 : (uint64_t)(a.i % b.i);  // (MIN % -1 is 0 in Java; it traps in C++)
+      break;
+    case DQ_AR_NEG: r = 0 - x; break;
+    default: return kNullV;
+  }
+  return V{2, 0, wrap_int((int64_t)r, rt), 0.0, nullptr};
+}
+
+// UTF8String.numChars: one per lead byte (a malformed sequence counts its stray bytes)
+DQ_DEV int32_t utf8_chars(const uint8_t* p, int32_t len) {
+  DevBytes rd{p};
+  int32_t n = 0;
+  for (int32_t k = 0; k < len; ++k) n += (rd.u8(k) & 0xC0u) != 0x80u;
+  return n;
+}
+
+// ------------------------------------------------------------------------------------------------
+// LIKE (DQ_X_LIKE): the host-compiled pattern program (LIT / ANY1 / ANYSEQ tokens, validated by
+// dq_plan_create) against a row's bytes.  The shapes `lit`, `lit%`, `%lit`, `%lit%`, `lit%lit`
+// (LikeShape, decided on the host) are loops over a byte range known on entry; everything else runs
+// like_general.
+// ------------------------------------------------------------------------------------------------
+// text[at .. at + len) == lit[0 .. len): four bytes at a time (a dword read that starts inside the
+// string never leaves the allocation: DevBytes), then the tail
+DQ_DEV bool bytes_eq(DevBytes text, int32_t at, DevBytes lit, int32_t lit_at, int32_t len) {
+  int32_t k = 0;
+  for (; k + 4 <= len; k += 4)
+    if (text.u32(at + k) != lit.u32(lit_at + k)) return false;
+  for (; k < len; ++k)
+    if (text.u8(at + k) != lit.u8(lit_at + k)) return false;
+  return true;
+}
+
+// bytes of the UTF-8 sequence a lead byte starts (a stray continuation byte: 1)
+DQ_DEV int32_t utf8_len(uint32_t b) { return b < 0xC0u ? 1 : (b < 0xE0u ? 2 : (b < 0xF0u ? 3 : 4)); }
+
+// %lit%: the first byte of the literal is looked for one aligned dword of text at a time
+DQ_DEV bool like_contains(DevBytes text, int32_t n, DevBytes prog, int32_t lit_at, int32_t m) {
+  if (m > n) return false;
+  const uint32_t c0 = prog.u8(lit_at);
+  const int32_t last = n - m;  // last start position
+  const uintptr_t a = reinterpret_cast<uintptr_t>(text.p);
+  const int32_t lead = (int32_t)(a & 3);  // text.p[0] is byte `lead` of its dword
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(a - lead);
+  const int32_t n_dw = (lead + last) / 4 + 1;  // dwords holding a start position
+  for (int32_t q = 0; q < n_dw; ++q) {
+    const uint32_t x = w[q];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int32_t s = q * 4 + j - lead;
+      if (s >= 0 && s <= last && ((x >> (8 * j)) & 0xffu) == c0 && bytes_eq(text, s + 1, prog, lit_at + 1, m - 1))
+        return true;
+    }
+  }
+  return false;
+}
+
+// The general case: the wildcard matcher with one backtrack point (the latest ANYSEQ and the text
+// position it is tried at, which moves on by one code point per retry).  Every retry moves that
+// position forward and at most every token runs between two retries, so (n + 2) * (tokens + 2)
+// steps decide every row; the loop counts them and has no other way to keep running.
+DQ_DEV bool like_general(DevBytes text, int32_t n, DevBytes prog, int32_t nb) {
+  int32_t ti = 0, pi = 0, star_pi = -1, star_ti = 0;
+  const int64_t bound = ((int64_t)n + 2) * ((int64_t)nb + 2);
+  for (int64_t step = 0; step < bound; ++step) {
+    if (pi < nb) {
+      const uint32_t kind = prog.u8(pi);
+      if (kind == DQ_LIKE_ANYSEQ) {
+        star_pi = ++pi;
+        star_ti = ti;
+        continue;
+      }
+      if (kind == DQ_LIKE_ANY1) {
+        if (ti < n) {
+          ti += utf8_len(text.u8(ti));
+          if (ti > n) ti = n;
+          ++pi;
+          continue;
+        }
+      } else {
+        const int32_t len = (int32_t)(prog.u8(pi + 1) | (prog.u8(pi + 2) << 8));
+        if (len <= n - ti && bytes_eq(text, ti, prog, pi + 3, len)) {
+          ti += len;
+          pi += 3 + len;
+          continue;
+        }
+      }
+    } else if (ti == n) {
+      return true;
+    }
+    // mismatch: retry the latest ANYSEQ one code point further on
+    if (star_pi < 0 || star_ti >= n) return false;
+    star_ti += utf8_len(text.u8(star_ti));
+    if (star_ti > n) star_ti = n;
+    ti = star_ti;
+    pi = star_pi;
+  }
+  return false;
+}
+
+DQ_DEV bool like_match(const uint8_t* s, int32_t n, const uint8_t* program, int32_t nb, int shape) {
+  const DevBytes text{s}, prog{program};
+  if (shape == LK_GENERAL) return like_general(text, n, prog, nb);
+  if (shape == LK_ALL) return true;
+  // a fast shape's literals are whole LIT tokens [kind, u16 length, bytes]; the first one follows
+  // the leading ANYSEQ of %lit and %lit% (the empty pattern has none: length 0)
+  const int32_t t1 = shape == LK_SUFFIX || shape == LK_CONTAINS ? 1 : 0;
+  const int32_t l1 = nb >= 3 ? (int32_t)(prog.u8(t1 + 1) | (prog.u8(t1 + 2) << 8)) : 0;
+  switch (shape) {
+    case LK_EQ: return n == l1 && bytes_eq(text, 0, prog, 3, l1);
+    case LK_PREFIX: return n >= l1 && bytes_eq(text, 0, prog, 3, l1);
+    case LK_SUFFIX: return n >= l1 && bytes_eq(text, n - l1, prog, 4, l1);
+    case LK_CONTAINS: return like_contains(text, n, prog, 4, l1);
+    case LK_ENDS: {
+      const int32_t at2 = 3 + l1 + 1;  // the second LIT token, after the ANYSEQ
+      const int32_t l2 = (int32_t)(prog.u8(at2 + 1) | (prog.u8(at2 + 2) << 8));
+      return n >= l1 + l2 && bytes_eq(text, 0, prog, 3, l1) && bytes_eq(text, n - l2, prog, at2 + 3, l2);
+    }
+    default: return false;
+  }
+}
+
 __global__ void __launch_bounds__(kBlock) expr_kernel(const XInstr* __restrict__ prog, int n_instr,
                                                       const DevCol* __restrict__ cols,
                                                       const uint8_t* __restrict__ pool, int64_t rows,
@@ -340,6 +540,46 @@ __global__ void __launch_bounds__(kBlock) expr_kernel(const XInstr* __restrict__
             }
             if (!status[q]) q = nx[q * nc + nc - 1];  // end of text
             a = V{1, 0, status[q] == 1 ? 1 : 0, 0.0, nullptr};
+            break;
+          }
+          case XI_LIKE: {  // a = program bytes | LikeShape << 16
+            V& a = st[sp - 1];
+            if (a.tag != 4) {  // NULL (or, past the host's typing, not a string): NULL
+              a = kNullV;
+              break;
+            }
+            const bool m = like_match(a.p, a.len, pool + ins.imm, ins.a & 0xffff, ins.a >> 16);
+            a = V{1, 0, m ? 1 : 0, 0.0, nullptr};
+            break;
+          }
+          case XI_ARITH: {  // a = dq_arith_op | result dq_type << 8
+            const int which = ins.a & 0xff, rt = ins.a >> 8;
+            if (which != DQ_AR_NEG) --sp;
+            st[sp - 1] = arith_eval(st[sp - 1], st[which != DQ_AR_NEG ? sp : sp - 1], which, rt);
+            break;
+          }
+          case XI_FUNC: {  // a = dq_func | result dq_type << 8, imm = number of arguments
+            const int which = ins.a & 0xff, rt = ins.a >> 8;
+            V& a = st[sp - 1];
+            if (which == DQ_FN_COALESCE) {  // the first non-NULL argument, in the common type
+              const int n = (int)ins.imm;
+              const int base = sp - n;
+              V res = kNullV;
+              for (int q = n - 1; q >= 0; --q)
+                if (st[base + q].tag != 0) res = st[base + q];
+              sp = base;
+              st[sp++] = rt == DQ_UTF8 ? res : to_num_type(res, rt);
+            } else if (which == DQ_FN_ISNAN) {  // FALSE, not NULL, on a NULL operand
+              a = V{1, 0, a.tag == 3 && a.d != a.d ? 1 : 0, 0.0, nullptr};
+            } else if (which == DQ_FN_LENGTH) {
+              a = a.tag == 4 ? V{2, 0, utf8_chars(a.p, a.len), 0.0, nullptr} : kNullV;
+            } else if (a.tag == 3) {  // DQ_FN_ABS
+              a.d = __builtin_fabs(a.d);
+            } else if (a.tag == 2) {
+              a.i = wrap_int((int64_t)(a.i < 0 ? 0 - (uint64_t)a.i : (uint64_t)a.i), rt);
+            } else {
+              a = kNullV;
+            }
             break;
           }
           default: break;

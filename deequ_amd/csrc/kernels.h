@@ -115,7 +115,22 @@ enum XiOp : int32_t {
   XI_CAST_F64,
   XI_REGEX,      // a = null_mode, imm = offset of the automaton in the pool
   XI_DEC128,     // imm = low word of a decimal literal (unscaled at its column's scale) ...
-  XI_DEC128_HI   // ... imm = its high word (always right after XI_DEC128)
+  XI_DEC128_HI,  // ... imm = its high word (always right after XI_DEC128)
+  XI_LIKE,       // a = program bytes | LikeShape << 16, imm = offset of the program in the pool
+  XI_ARITH,      // a = dq_arith_op | result dq_type << 8
+  XI_FUNC        // a = dq_func | result dq_type << 8, imm = number of arguments
+};
+
+// What a LIKE pattern program is, decided on the host (api.cpp like_shape) so that the shapes
+// nearly every pattern has run as one pass over the row's bytes.
+enum LikeShape : int32_t {
+  LK_GENERAL = 0,  // anything else: the one-backtrack-point matcher
+  LK_EQ,           // lit (also the empty pattern)
+  LK_PREFIX,       // lit%
+  LK_SUFFIX,       // %lit
+  LK_CONTAINS,     // %lit%
+  LK_ENDS,         // lit%lit
+  LK_ALL           // %
 };
 
 struct XInstr {

@@ -10,14 +10,30 @@ Compliance.scala:47-49).  The strings Check generates are (Check.scala):
   * ``isContainedIn``        ``"c IS NULL OR c IN ('v1','v2')"`` (quotes doubled)    :826-840
   * numeric range            ``"c IS NULL OR (c >= lo AND c <= hi)"``                :853-869
 
-This module parses that grammar (plus NOT, parentheses, <>, !=, <=>, BETWEEN, booleans, NULL and
-CAST(x AS DOUBLE)) and applies Spark 2.2's type coercion so the engine only sees typed operations:
+This module parses that grammar (plus NOT, parentheses, <>, !=, <=>, BETWEEN, booleans, NULL,
+CAST(x AS DOUBLE / FLOAT), RLIKE, LIKE, arithmetic and six scalar functions) with Spark 2.2's
+precedence -- OR < AND < NOT < comparison / IS / IN / BETWEEN / LIKE / RLIKE < ``+ -`` <
+``* / %`` < unary ``- +`` < primary -- and applies Spark 2.2's type coercion so the engine only
+sees typed operations:
 
   * numeric vs numeric: compared in the wider type (integral -> int64, else double);
   * string vs numeric: the string side is CAST to DOUBLE (Spark 2.2 ``PromoteStrings``);
   * ``x IN (...)`` with mixed item types: numeric literals in a string list become strings
     (``InConversion`` -> ``findWiderCommonType`` with string promotion); a numeric column or
-    cast IN a list of strings, which Spark casts to STRING row by row, raises :class:`SqlError`.
+    cast IN a list of strings, which Spark casts to STRING row by row, raises :class:`SqlError`;
+  * ``x [NOT] LIKE 'pattern'`` over a string operand: the literal is unescaped as Spark's
+    ``unescapeSQLString`` does (``\\%`` and ``\\_`` keep their backslash) and read as
+    ``StringUtils.escapeLikeRegex`` reads it (``%`` any sequence, ``_`` one code point, ``\\%``
+    ``\\_`` ``\\\\`` literals, any other escape an error), then compiled into a small pattern
+    program (LIT / ANY1 / ANYSEQ tokens) for the device's own matcher -- never into a regex;
+  * ``+ - * / %`` and unary ``-``: the result type follows ``numericPrecedence`` (Byte < Short <
+    Int < Long < Float < Double; an integer literal is Int if it fits, else Long), integral
+    results wrap at that width, ``/`` is always a double division, ``/`` and ``%`` by zero are
+    NULL, a string operand is CAST to DOUBLE; a fractional literal without a ``D`` suffix is a
+    decimal literal: cast to double against a float / double / string operand, refused against
+    an integral or decimal one (Spark does decimal arithmetic there);
+  * ``abs``, ``length``, ``coalesce`` (2 to 8 arguments), ``isnan``, ``isnull``, ``isnotnull``;
+    every other function raises :class:`SqlError`.
 
 Column names resolve case-insensitively (spark.sql.caseSensitive=false).  Anything outside the
 grammar raises :class:`SqlError`, which the runner turns into a failure of the shared scan exactly
@@ -45,7 +61,7 @@ _TOKEN = re.compile(r"""
       (?P<num>(?:\d+\.\d*|\.\d+|\d+)(?:[eE][+-]?\d+)?[LDSYlfdsyBD]{0,2})|
       (?P<str>'(?:[^'\\]|''|\\.)*'|"(?:[^"\\]|\\.)*")|
       (?P<bq>`(?:[^`]|``)+`)|
-      (?P<op><=>|<=|>=|<>|!=|==|=|<|>|\(|\)|,|\+|-|\*|/)|
+      (?P<op><=>|<=|>=|<>|!=|==|=|<|>|\(|\)|,|\+|-|\*|/|%)|
       (?P<id>[A-Za-z_][A-Za-z0-9_.]*)
     )""", re.VERBOSE)
 
@@ -76,7 +92,8 @@ def tokenize(s: str) -> List[Tok]:
 # ------------------------------------------------------------------------------------------------
 @dataclass
 class Node:
-    op: str                      # col, lit, isnull, isnotnull, not, and, or, cmp, in, cast
+    op: str                      # col, lit, isnull, isnotnull, not, and, or, cmp, in, cast, regex,
+                                 # like, arith (name = + - * / %), neg, func (name = the function)
     kids: List["Node"] = field(default_factory=list)
     name: Optional[str] = None   # column name / comparison symbol / cast type
     value: object = None         # literal value
@@ -85,9 +102,13 @@ class Node:
     # DoubleType (a D suffix; every other fractional / exponent literal is a DecimalType literal)
     exact: object = None
     dbl: bool = False
+    suffix: str = ""             # an integral literal's type suffix (L, S, Y)
 
 
-_KW = {"AND", "OR", "NOT", "IS", "NULL", "IN", "TRUE", "FALSE", "BETWEEN", "CAST", "AS", "RLIKE"}
+_KW = {"AND", "OR", "NOT", "IS", "NULL", "IN", "TRUE", "FALSE", "BETWEEN", "CAST", "AS", "RLIKE",
+       "LIKE"}
+_FUNCS = {"abs": (1, 1), "length": (1, 1), "coalesce": (2, 8), "isnan": (1, 1), "isnull": (1, 1),
+          "isnotnull": (1, 1)}   # name -> (fewest, most) arguments
 
 # The engine's spelling of PatternMatch's counted expression,
 # when(regexp_extract(x, pattern, 0) != "", 1).otherwise(0) (PatternMatch.scala:44-46): TRUE when
@@ -151,14 +172,14 @@ class _Parser:
         return self.predicate()
 
     def predicate(self) -> Node:
-        left = self.primary()
+        left = self.additive()
         t = self.peek()
         if t is None:
             return left
         if t.kind == "op" and t.text in ("=", "==", "<>", "!=", "<", "<=", ">", ">=", "<=>"):
             self.i += 1
             sym = {"==": "=", "!=": "<>"}.get(t.text, t.text)
-            return Node("cmp", [left, self.primary()], name=sym)
+            return Node("cmp", [left, self.additive()], name=sym)
         if self.kw("IS"):
             self.i += 1
             neg = False
@@ -170,9 +191,18 @@ class _Parser:
             self.i += 1
             return Node("isnotnull" if neg else "isnull", [left])
         neg = False
-        if self.kw("NOT") and self.kw("RLIKE", 1):
+        if self.kw("NOT") and (self.kw("RLIKE", 1) or self.kw("LIKE", 1)):
             self.i += 1
             neg = True
+        if self.kw("LIKE"):  # x LIKE 'pattern': the whole string must match, NULL on NULL
+            self.i += 1
+            t = self.peek()
+            if t is None or t.kind != "str":
+                raise SqlError("LIKE needs a string literal pattern")
+            self.i += 1
+            pat = _unescape_sql_string(t.text, like=True)
+            n = Node("like", [left], name=pat, value=like_program(pat))
+            return Node("not", [n]) if neg else n
         if self.kw("RLIKE"):  # x RLIKE 'java regex': find() anywhere, NULL on NULL
             self.i += 1
             pat = self.primary()
@@ -186,23 +216,49 @@ class _Parser:
         if self.kw("IN"):
             self.i += 1
             self.expect_sym("(")
-            items = [self.primary()]
+            items = [self.additive()]
             while self.sym(","):
                 self.i += 1
-                items.append(self.primary())
+                items.append(self.additive())
             self.expect_sym(")")
             n = Node("in", [left] + items)
             return Node("not", [n]) if neg else n
         if self.kw("BETWEEN"):
             self.i += 1
-            lo = self.primary()
+            lo = self.additive()
             if not self.kw("AND"):
                 raise SqlError("expected AND in BETWEEN")
             self.i += 1
-            hi = self.primary()
+            hi = self.additive()
             n = Node("and", [Node("cmp", [left, lo], name=">="), Node("cmp", [left, hi], name="<=")])
             return Node("not", [n]) if neg else n
         return left
+
+    def additive(self) -> Node:
+        n = self.multiplicative()
+        while self.sym("+") or self.sym("-"):
+            sym = self.take().text
+            n = Node("arith", [n, self.multiplicative()], name=sym)
+        return n
+
+    def multiplicative(self) -> Node:
+        n = self.unary()
+        while self.sym("*") or self.sym("/") or self.sym("%"):
+            sym = self.take().text
+            n = Node("arith", [n, self.unary()], name=sym)
+        return n
+
+    def unary(self) -> Node:
+        if self.sym("-") or self.sym("+"):
+            t = self.take()
+            inner = self.unary()
+            if inner.op == "lit" and inner.ltype in ("int", "float"):  # a constant: folded
+                if t.text == "-":
+                    inner.value = -inner.value
+                    inner.exact = -inner.exact if inner.exact is not None else None
+                return inner
+            return Node("neg", [inner]) if t.text == "-" else inner
+        return self.primary()
 
     def primary(self) -> Node:
         t = self.take()
@@ -211,21 +267,12 @@ class _Parser:
             self.expect_sym(")")
             return n
         if t.kind == "op" and t.text in ("-", "+"):
-            inner = self.primary()
-            if inner.op != "lit" or inner.ltype not in ("int", "float"):
-                raise SqlError("unary minus only supported on numeric literals")
-            if t.text == "-":
-                inner.value = -inner.value
-                inner.exact = -inner.exact if inner.exact is not None else None
-            return inner
+            self.i -= 1
+            return self.unary()
         if t.kind == "num":
             return _num_literal(t.text)
         if t.kind == "str":
-            q = t.text[0]
-            body = t.text[1:-1]
-            body = body.replace("''", "'") if q == "'" else body
-            body = re.sub(r"\\(.)", lambda m: {"n": "\n", "t": "\t", "0": "\0"}.get(m.group(1), m.group(1)), body)
-            return Node("lit", value=body, ltype="str")
+            return Node("lit", value=_unescape_sql_string(t.text), ltype="str")
         if t.kind == "bq":
             return Node("col", name=t.text[1:-1].replace("``", "`"))
         if t.kind == "id":
@@ -254,10 +301,89 @@ class _Parser:
                 if pat.op != "lit" or pat.ltype != "str":
                     raise SqlError(f"{FIND_NONEMPTY} needs a string literal pattern")
                 return Node("regex", [x], name="nonempty", value=pat.value)
+            if self.sym("(") and t.text.lower() in _FUNCS:
+                name = t.text.lower()
+                self.expect_sym("(")
+                args = [self.or_()]
+                while self.sym(","):
+                    self.i += 1
+                    args.append(self.or_())
+                self.expect_sym(")")
+                lo, hi = _FUNCS[name]
+                if not lo <= len(args) <= hi:
+                    raise SqlError(f"{name}() takes {lo} argument{'s' if lo > 1 else ''}"
+                                   + (f" to {hi}" if hi > lo else "") + f", not {len(args)}")
+                if name in ("isnull", "isnotnull"):  # the function spelling of IS [NOT] NULL
+                    return Node(name, args)
+                return Node("func", args, name=name)
             if self.sym("("):
                 raise SqlError(f"function {t.text}() is not supported by the engine")
             return Node("col", name=t.text)
         raise SqlError(f"unexpected token {t.text!r}")
+
+
+def _unescape_sql_string(text: str, like: bool = False) -> str:
+    """The value of a quoted SQL string token.  In a LIKE pattern ``\\%`` and ``\\_`` keep their
+    backslash, as Spark's ``unescapeSQLString`` leaves them for ``escapeLikeRegex``."""
+    q = text[0]
+    body = text[1:-1]
+    body = body.replace("''", "'") if q == "'" else body
+    esc = {"n": "\n", "t": "\t", "0": "\0"}
+    if like:
+        esc = dict(esc, **{"%": "\\%", "_": "\\_"})
+    return re.sub(r"\\(.)", lambda m: esc.get(m.group(1), m.group(1)), body)
+
+
+# Tokens of a LIKE pattern program (include/deequ_amd.h, DQ_X_LIKE)
+LIKE_LIT, LIKE_ANY1, LIKE_ANYSEQ = 1, 2, 3
+LIKE_MAX_BYTES = 4096
+
+
+def like_program(pattern: str) -> bytes:
+    """Compiles an (unescaped) LIKE pattern as Spark 2.2's ``StringUtils.escapeLikeRegex`` reads
+    it into the device matcher's token stream: LIT(u16 length, bytes), ANY1 (``_``: one code
+    point), ANYSEQ (``%``: any sequence; adjacent ones collapsed)."""
+    toks: List[object] = []
+
+    def lit(ch: str):
+        if toks and isinstance(toks[-1], bytearray):
+            toks[-1] += ch.encode("utf-8")
+        else:
+            toks.append(bytearray(ch.encode("utf-8")))
+
+    i = 0
+    while i < len(pattern):
+        c = pattern[i]
+        if c == "\\":
+            if i + 1 >= len(pattern):
+                raise SqlError(f"the pattern '{pattern}' is invalid, it is not allowed to end with "
+                               f"the escape character")
+            d = pattern[i + 1]
+            if d not in "_%\\":
+                raise SqlError(f"the pattern '{pattern}' is invalid, the escape character is not "
+                               f"allowed to precede '{d}'")
+            lit(d)
+            i += 2
+            continue
+        if c == "_":
+            toks.append(LIKE_ANY1)
+        elif c == "%":
+            if not toks or toks[-1] != LIKE_ANYSEQ:
+                toks.append(LIKE_ANYSEQ)
+        else:
+            lit(c)
+        i += 1
+    out = bytearray()
+    for t in toks:
+        if isinstance(t, bytearray):
+            if len(t) > 0xFFFF:
+                raise SqlError("LIKE pattern too long for the engine")
+            out += bytes([LIKE_LIT, len(t) & 0xFF, len(t) >> 8]) + t
+        else:
+            out.append(t)
+    if len(out) > LIKE_MAX_BYTES:
+        raise SqlError(f"LIKE pattern too long for the engine ({len(out)} > {LIKE_MAX_BYTES} bytes)")
+    return bytes(out)
 
 
 def _num_literal(text: str) -> Node:
@@ -267,7 +393,7 @@ def _num_literal(text: str) -> Node:
         from decimal import Decimal
         return Node("lit", value=float(body), ltype="float", exact=Decimal(body), dbl=suffix == "D")
     if suffix in ("", "L", "S", "Y"):
-        return Node("lit", value=int(body), ltype="int", exact=int(body))
+        return Node("lit", value=int(body), ltype="int", exact=int(body), suffix=suffix)
     raise SqlError(f"bad numeric literal {text}")
 
 
@@ -339,7 +465,85 @@ class _Emitter:
         if n.op == "cast":
             return {"DOUBLE": "float", "FLOAT": "float", "STRING": "str", "INT": "int",
                     "BIGINT": "int", "LONG": "int", "BOOLEAN": "bool"}.get(n.name, "?")
+        if n.op in ("arith", "neg") or (n.op == "func" and n.name != "isnan"):
+            t = self.result_type(n)
+            return "str" if t == N.UTF8 else ("int" if t in N.INTEGRAL_TYPES else "float")
         return "bool"
+
+    # -- arithmetic and functions: Spark 2.2 result types, widths included
+    def operand_type(self, n: Node, what: str):
+        """What an operand of ``what`` (an arithmetic operator or a function) is: a dq_type in
+        INT8..FLOAT64, "str", "null" or "declit" (a DecimalType literal).  Anything else has no
+        arithmetic in the interpreter and is refused."""
+        if n.op == "lit":
+            if n.ltype == "int":
+                t = {"L": N.INT64, "S": N.INT16, "Y": N.INT8}.get(n.suffix)
+                return t or (N.INT32 if -(1 << 31) <= n.value < (1 << 31) else N.INT64)
+            if n.ltype == "float":
+                return N.FLOAT64 if n.dbl else "declit"
+            if n.ltype in ("str", "null"):
+                return n.ltype
+        elif n.op == "col":
+            kind = self.type_of(n)
+            if kind in ("int", "float"):
+                return self.schema[n.name].dtype
+            if kind == "str":
+                return "str"
+            if kind == "dec":
+                raise SqlError(f"{what} over a decimal column: Spark does decimal arithmetic, "
+                               f"which is not supported by the engine")
+        elif n.op == "cast" and n.name in ("DOUBLE", "FLOAT"):
+            return N.FLOAT64 if n.name == "DOUBLE" else N.FLOAT32
+        elif n.op in ("arith", "neg", "func") and self.type_of(n) != "bool":
+            t = self.result_type(n)
+            return "str" if t == N.UTF8 else t
+        raise SqlError(f"{what} over a {self.type_of(n)} operand is not supported by the engine")
+
+    def promote(self, types, what: str) -> int:
+        """numericPrecedence over operand types: a string is cast to DOUBLE (PromoteStrings), a
+        decimal literal to double beside a float / double / string operand."""
+        nums = [t for t in types if t not in ("null", "declit", "str")]
+        if "declit" in types and not ("str" in types or any(t in (N.FLOAT32, N.FLOAT64) for t in nums)):
+            raise SqlError(f"{what} of a fractional (decimal) literal and an integral or decimal "
+                           f"operand: Spark does decimal arithmetic, which is not supported by the "
+                           f"engine (write the literal with a D suffix for double arithmetic)")
+        if "declit" in types or "str" in types:
+            return N.FLOAT64
+        if not nums:
+            raise SqlError(f"{what} over NULL operands only is not supported by the engine")
+        return max(nums)  # (the dq_type values ascend Byte < Short < Int < Long < Float < Double)
+
+    def result_type(self, n: Node) -> int:
+        """The dq_type an arith / neg / func node evaluates to (UTF8: coalesce over strings)."""
+        if n.op == "neg":
+            return self.promote([self.operand_type(n.kids[0], "unary -")], "unary -")
+        if n.op == "arith":
+            t = self.promote([self.operand_type(k, f"'{n.name}'") for k in n.kids], f"'{n.name}'")
+            return N.FLOAT64 if n.name == "/" else t  # the Division rule: always a double division
+        what = f"{n.name}()"
+        types = [self.operand_type(k, what) for k in n.kids]
+        if n.name == "length":
+            if types != ["str"]:
+                raise SqlError("length() needs a string operand")
+            return N.INT32
+        if n.name == "isnan":
+            if types[0] not in (N.FLOAT32, N.FLOAT64):
+                raise SqlError("isnan() needs a float or double operand")
+            return N.BOOL
+        if n.name == "coalesce" and all(t in ("str", "null") for t in types) and "str" in types:
+            return N.UTF8
+        if n.name == "coalesce" and "str" in types:
+            raise SqlError("coalesce() over string and numeric arguments is not supported by the "
+                           "engine")
+        return self.promote(types, what)
+
+    def emit_operand(self, k: Node, what: str):
+        """An operand of an arithmetic operator / numeric function: a string under CAST AS DOUBLE,
+        a decimal literal as its double."""
+        t = self.operand_type(k, what)
+        if t == "str":
+            self.words.append(N.X_CAST_F64)
+        self.emit(k, "float" if t == "declit" else None)
 
     def emit(self, n: Node, want: Optional[str] = None):
         w = self.words
@@ -453,6 +657,37 @@ class _Emitter:
             w += list(struct.unpack(f"<{len(padded) // 8}q", padded))
             self.emit(n.kids[0])
             return
+        if n.op == "like":
+            if self.type_of(n.kids[0]) != "str":
+                # Spark casts the operand to string; the interpreter has no such cast outside
+                # the regex op
+                raise SqlError(f"LIKE over a {self.type_of(n.kids[0])} operand (Spark casts it to "
+                               f"STRING) is not supported by the engine")
+            blob = n.value
+            w += [N.X_LIKE, len(blob)]
+            padded = blob + b"\0" * ((-len(blob)) % 8)
+            w += list(struct.unpack(f"<{len(padded) // 8}q", padded)) if padded else []
+            self.emit(n.kids[0])
+            return
+        if n.op in ("arith", "neg"):
+            what = "unary -" if n.op == "neg" else f"'{n.name}'"
+            which = N.AR_NEG if n.op == "neg" else _ARITH[n.name]
+            w += [N.X_ARITH, which, self.result_type(n)]
+            for k in n.kids:
+                self.emit_operand(k, what)
+            return
+        if n.op == "func":
+            rt = self.result_type(n)
+            if n.name == "coalesce":
+                w += [N.X_FUNC, N.FN_COALESCE, rt, len(n.kids)]
+            else:
+                w += [N.X_FUNC, _FUNC_CODE[n.name], rt, 1]
+            for k in n.kids:
+                if rt == N.UTF8 or n.name in ("length", "isnan"):
+                    self.emit(k)
+                else:
+                    self.emit_operand(k, f"{n.name}()")
+            return
         raise SqlError(f"unsupported expression node {n.op}")
 
     # -- decimal columns (Spark 2.2 DecimalPrecision: exact against integral / decimal literals,
@@ -513,6 +748,8 @@ class _Emitter:
 
 
 _FLIP = {"<": ">", "<=": ">=", ">": "<", ">=": "<="}
+_ARITH = {"+": N.AR_ADD, "-": N.AR_SUB, "*": N.AR_MUL, "/": N.AR_DIV, "%": N.AR_MOD}
+_FUNC_CODE = {"abs": N.FN_ABS, "length": N.FN_LENGTH, "isnan": N.FN_ISNAN}
 
 
 _REGEX_CACHE = {}
@@ -563,7 +800,7 @@ def compile_expr(sql: str, schema, col_index) -> CompiledExpr:
     node = parse(sql)
     em = _Emitter(schema, col_index)
     t = em.type_of(node) if node.op != "col" else em.type_of(node)
-    if t not in ("bool", "null") and node.op in ("col", "lit"):
+    if t not in ("bool", "null") and node.op in ("col", "lit", "arith", "neg", "func"):
         if t != "bool":
             raise SqlError(f"expression '{sql}' is not a predicate")
     em.emit(node)

@@ -184,7 +184,7 @@ typedef enum dq_xop {
                           then prints as Float.toString.  A string x (utf8 column or literal)
                           is refused by dq_plan_create with DQ_ERR_UNSUPPORTED:
                           Float.parseFloat's direct rounding is not restated.                  */
-  DQ_X_DEC128 = 23     /* [op, lo, hi]  decimal literal as an unscaled 128-bit value at the scale of
+  DQ_X_DEC128 = 23,    /* [op, lo, hi]  decimal literal as an unscaled 128-bit value at the scale of
                           the DQ_DECIMAL128 column it is compared with (the host rescales it, so
                           the comparison is exact, as Spark's DecimalPrecision makes it).  A
                           decimal column may appear under IS [NOT] NULL, in comparisons / IN with
@@ -192,7 +192,40 @@ typedef enum dq_xop {
                           rounded) and as a regex operand (BigDecimal.toString text); a date /
                           timestamp column under IS [NOT] NULL and as a regex operand.  Any other
                           use is refused by dq_plan_create with DQ_ERR_UNSUPPORTED.            */
+  DQ_X_LIKE = 24,      /* [op, nbytes, ceil(n/8) words, x]  x LIKE pattern over a string x (the
+                          whole string must match; NULL on a NULL x).  The words pack a pattern
+                          program the host compiled (escapes resolved, adjacent % collapsed): a
+                          stream of tokens DQ_LIKE_LIT (then a little-endian u16 length >= 1 and
+                          that many bytes), DQ_LIKE_ANY1 (_: one UTF-8 sequence) and
+                          DQ_LIKE_ANYSEQ (%: any byte sequence), at most DQ_LIKE_MAX_BYTES bytes.
+                          dq_plan_create checks every token kind and length before any device
+                          code reads the program.                                              */
+  DQ_X_ARITH = 25,     /* [op, which, result_type, a, b]  a dq_arith_op over numeric operands (b
+                          absent for DQ_AR_NEG); result_type is the dq_type in DQ_INT8 ..
+                          DQ_FLOAT64 Spark 2.2 gives the result (DQ_AR_DIV: DQ_FLOAT64).  Both
+                          operands are converted to it, integral results wrap at its width (Java),
+                          a DQ_FLOAT32 result is computed in float.  NULL when an operand is
+                          NULL, and for / and % when the divisor equals 0 (0.0, -0.0).  % takes
+                          the dividend's sign (Java's %, fmod for floats).                      */
+  DQ_X_FUNC = 26       /* [op, which, result_type, n_args, args...]  a dq_func.  DQ_FN_ABS (1
+                          numeric argument; abs(MIN) wraps), DQ_FN_LENGTH (1 string argument;
+                          result_type DQ_INT32: the number of code points), DQ_FN_COALESCE (2-8
+                          arguments, all numeric -- converted to result_type -- or all strings,
+                          result_type DQ_UTF8: the first non-NULL one), DQ_FN_ISNAN (1 float /
+                          double argument; result_type DQ_BOOL; FALSE on NULL).  An expression
+                          holding one of these three operators is always evaluated by the
+                          generic interpreter (an expression bitmap), never fused.            */
 } dq_xop;
+
+typedef enum dq_arith_op {
+  DQ_AR_ADD = 1, DQ_AR_SUB = 2, DQ_AR_MUL = 3, DQ_AR_DIV = 4, DQ_AR_MOD = 5, DQ_AR_NEG = 6
+} dq_arith_op;
+
+typedef enum dq_func {
+  DQ_FN_ABS = 1, DQ_FN_LENGTH = 2, DQ_FN_COALESCE = 3, DQ_FN_ISNAN = 4
+} dq_func;
+
+enum { DQ_LIKE_LIT = 1, DQ_LIKE_ANY1 = 2, DQ_LIKE_ANYSEQ = 3, DQ_LIKE_MAX_BYTES = 4096 };
 
 typedef struct dq_expr {
   const int64_t* words;
