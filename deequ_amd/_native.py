@@ -68,6 +68,10 @@ def type_name(t: int) -> str:
 AR_ADD, AR_SUB, AR_MUL, AR_DIV, AR_MOD, AR_NEG = range(1, 7)
 FN_ABS, FN_LENGTH, FN_COALESCE, FN_ISNAN = range(1, 5)
 
+# dq_index_type (the integers of a dictionary column's indices)
+(INDEX_INT8, INDEX_UINT8, INDEX_INT16, INDEX_UINT16, INDEX_INT32, INDEX_UINT32, INDEX_INT64,
+ INDEX_UINT64) = range(1, 9)
+
 # dq_agg_kind
 (AGG_COUNT_ALL, AGG_COUNT_NOTNULL, AGG_COUNT_TRUE, AGG_SUM, AGG_MIN, AGG_MAX, AGG_STDDEV_POP,
  AGG_CORR, AGG_HLL, AGG_DTYPE) = range(1, 11)
@@ -201,6 +205,10 @@ def _load() -> ctypes.CDLL:
                                    POINTER(dq_column), c_int, POINTER(c_int64), c_void_p]),
         "dq_gather_column": (c_int, [POINTER(dq_column), c_void_p, c_int64, POINTER(dq_column),
                                      c_void_p]),
+        "dq_dict_decode": (c_int, [POINTER(dq_column), c_int, POINTER(dq_column), POINTER(dq_column),
+                                   POINTER(c_int64), c_void_p]),
+        "dq_freq_add_dict_device": (c_int, [c_void_p, POINTER(dq_column), c_int, POINTER(dq_column),
+                                            c_int, c_void_p]),
         "dq_freq_import": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                    c_int64, c_int, c_void_p]),
         "dq_freq_num_rows": (c_int64, [c_void_p]),
@@ -251,6 +259,7 @@ EXPORTED = [
     "dq_freq_add_host", "dq_freq_partition_sizes", "dq_freq_partition",
     "dq_freq_add_records_device", "dq_key_partition",
     "dq_schema_evaluate", "dq_select_plan", "dq_gather_column",
+    "dq_dict_decode", "dq_freq_add_dict_device",
 ]
 FREQ_RECORD_BYTES = 24  # sizeof(dq_freq_record)
 

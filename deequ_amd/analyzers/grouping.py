@@ -38,6 +38,7 @@ class FrequencyTable:
         h = ctypes.c_void_p()
         N.check(N.lib.dq_freq_create(device, len(key_types), types, capacity_hint, ctypes.byref(h)))
         self.handle = h
+        self.encoded_batches = 0  # batches added through dq_freq_add_dict_device
 
     def __del__(self):
         try:
@@ -47,11 +48,23 @@ class FrequencyTable:
         except Exception:  # noqa: BLE001
             pass
 
-    def add(self, columns: Sequence, null_as_group: bool = False, stream=None) -> None:
-        arr = (N.dq_column * len(columns))(*[c.to_c() for c in columns])
+    def add(self, columns: Sequence, null_as_group: bool = False, stream=None,
+            encoded: bool = False) -> None:
+        """Adds one batch.  encoded: a one-key table whose batch holds the encoded pair of a
+        dictionary column (ColumnBatch.encoded) counts the indices per entry instead of reading
+        the decoded column (dq_freq_add_dict_device); any other batch takes the decoded columns."""
         if stream is None:
             import torch
             stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        enc = getattr(columns[0], "encoded", None) if encoded and len(columns) == 1 else None
+        if enc is not None and len(self.key_types) == 1:
+            cidx, cdict = enc.indices_c(), enc.dictionary.to_c()
+            N.check(N.lib.dq_freq_add_dict_device(self.handle, ctypes.byref(cidx), enc.index_type,
+                                                  ctypes.byref(cdict), 1 if null_as_group else 0,
+                                                  stream))
+            self.encoded_batches += 1
+            return
+        arr = (N.dq_column * len(columns))(*[c.to_c() for c in columns])
         N.check(N.lib.dq_freq_add_device(self.handle, arr, len(columns), 1 if null_as_group else 0,
                                          stream))
 
@@ -327,7 +340,7 @@ def compute_frequencies(data, grouping_columns: Sequence[str],
     table = FrequencyTable(grouping_columns, types, data.device_index(),
                            capacity_hint=data.num_rows)  # sized once: no growth copies
     for batch in data.batches:
-        table.add([batch[c] for c in grouping_columns])
+        table.add([batch[c] for c in grouping_columns], encoded=True)
     n = num_rows if num_rows is not None else data.count()
     return FrequenciesAndNumRows(table, n)
 
@@ -763,7 +776,7 @@ class Histogram(Analyzer):
         total = data.count()
         table = FrequencyTable([self.column], [dtype], data.device_index(), capacity_hint=total)
         for batch in data.batches:
-            table.add([batch[self.column]], null_as_group=True)
+            table.add([batch[self.column]], null_as_group=True, encoded=True)
         return HistogramState(table, total, dtype, self.binning_udf)
 
     def compute_metric_from(self, state):

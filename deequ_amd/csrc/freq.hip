@@ -7492,6 +7492,133 @@ static dq_status add_records(dq_freq* f, const dq_freq_record* records, const ui
 }
 
 // ------------------------------------------------------------------------------------------------
+// Dictionary-encoded key column (Arrow dictionary<I, V>): the batch already holds its grouping, one
+// small integer per row.  The rows are counted per entry (dict.hip, launch_dict_count), then every
+// used non-NULL entry becomes ONE record -- exact mode: its canonical widened value; hashed mode:
+// its row hash with the encoded key in the var bytes -- and the records go through add_records,
+// which adds counts of equal keys (duplicate entries) and keeps equal hashes with different keys
+// apart.  An entry is hashed and encoded once, not once per row.
+// ------------------------------------------------------------------------------------------------
+namespace dq {
+
+// words: [0] records written, [1] var bytes written, [2] rows of NULL entries, [3] rows whose NaN
+// payload the Histogram mode folded (C_NAN_FOLDED, as the row path counts it)
+__global__ void __launch_bounds__(256)
+freq_dict_records(KeySet ks, int exact, int64_t entries, const unsigned long long* __restrict__ counts,
+                  RecIn* __restrict__ recs, uint8_t* __restrict__ var,
+                  unsigned long long* __restrict__ words) {
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < entries; e += (int64_t)gridDim.x * 256) {
+    const unsigned long long c = counts[e];
+    if (!c) continue;
+    if (!kbit(ks.cols[0].valid, e)) {
+      atomicAdd(words + 2, c);
+      continue;
+    }
+    RecIn r;
+    r.count = c;
+    r.enc_off = 0;
+    if (exact) {
+      const uint64_t raw = kwiden(ks.cols[0].type, ks.cols[0].values, e);
+      r.key = exact_canon(ks, raw);
+      if (r.key != raw) atomicAdd(words + 3, c);
+    } else {  // (one key and hashed: a utf8 key)
+      const SView v = str1_view(ks, e);
+      const uint32_t enc = str1_enc_size(ks, e), sz = (enc + 7u) & ~7u;
+      const unsigned long long at = atomicAdd(words + 1, (unsigned long long)sz);
+      uint32_t* dst = reinterpret_cast<uint32_t*>(var + at);
+      str1_encode(ks, e, dst);
+      if (sz != enc) dst[enc / 4] = 0;
+      r.key = str_row_hash(v);
+      r.enc_off = at;
+    }
+    recs[atomicAdd(words, 1ull)] = r;
+  }
+}
+
+}  // namespace dq
+
+extern "C" dq_status dq_freq_add_dict_device(dq_freq* f, const dq_column* indices, int index_type,
+                                             const dq_column* dictionary, int null_as_group,
+                                             void* hip_stream) {
+  if (!f || !indices || !dictionary) return fail(DQ_ERR_INVALID_ARGUMENT, "null argument");
+  if (f->n_keys != 1) return fail(DQ_ERR_UNSUPPORTED, "an encoded batch needs a one-key table");
+  if (!dict_index_type_ok(index_type)) return fail(DQ_ERR_INVALID_ARGUMENT, "index type %d", index_type);
+  if (dictionary->type != f->logical[0]) return fail(DQ_ERR_WRONG_TYPE, "the dictionary has the wrong type");
+  if (f->arena_view) return fail(DQ_ERR_STATE, "a table reading another table's keys takes no adds");
+  const int mode = null_as_group ? 1 : 0;
+  if (f->mode_null_as_group >= 0 && f->mode_null_as_group != mode)
+    return fail(DQ_ERR_STATE, "null_as_group must be the same for every batch");
+  const int64_t rows = indices->length, entries = dictionary->length;
+  if (rows < 0 || entries < 0) return fail(DQ_ERR_INVALID_ARGUMENT, "negative length");
+  if (rows > 2147483647LL || entries > 2147483647LL)
+    return fail(DQ_ERR_UNSUPPORTED, "an encoded batch of more than 2^31-1 rows or entries");
+  if (rows && !indices->values) return fail(DQ_ERR_INVALID_ARGUMENT, "null indices");
+  if (entries && (!dictionary->values || (DQ_TYPE_ID(dictionary->type) == DQ_UTF8 && !dictionary->data)))
+    return fail(DQ_ERR_INVALID_ARGUMENT, "null dictionary buffers");
+  HIP_TRY(hipSetDevice(f->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  // counts[entries], then: bad indices, NULL indices, and freq_dict_records' four words
+  DevBuf<unsigned long long> cnt;
+  HIP_TRY(cnt.ensure((size_t)entries + 8));
+  HIP_TRY(hipMemsetAsync(cnt.p, 0, ((size_t)entries + 8) * sizeof(unsigned long long), st));
+  unsigned long long* words = cnt.p + entries;
+  HIP_TRY(launch_dict_count(indices->values, index_type, indices->validity, rows, entries, cnt.p, words, st));
+  unsigned long long h[2] = {0, 0};
+  HIP_TRY(d2h(h, words, sizeof(h), st));
+  if (h[0])  // (nothing of the table was touched)
+    return fail(DQ_ERR_INVALID_ARGUMENT, "%llu of the %lld rows hold an index outside [0, %lld)", h[0],
+                (long long)rows, (long long)entries);
+  dq_column dphys = *dictionary;
+  if (f->relabel) {
+    const dq_status ps = physical_keys(f, dictionary, 1, st, &dphys);
+    if (ps != DQ_OK) return ps;
+  }
+  uint64_t var_bound = 8;
+  if (!f->exact && entries) {  // per entry: tag, length, the bytes padded to 4, the record's pad to 8
+    int64_t bytes = dphys.data_bytes;
+    if (bytes <= 0) {
+      int32_t first = 0, last = 0;
+      HIP_TRY(hipStreamSynchronize(st));
+      HIP_TRY(hipMemcpy(&first, dphys.values, 4, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(&last, reinterpret_cast<const int32_t*>(dphys.values) + entries, 4,
+                        hipMemcpyDeviceToHost));
+      if (last < first) return fail(DQ_ERR_INVALID_ARGUMENT, "the dictionary has bad offsets");
+      bytes = last - first;
+    }
+    var_bound = 16 * (uint64_t)entries + (uint64_t)bytes + 8;
+  }
+  DevBuf<RecIn> recs;
+  DevBuf<uint8_t> var;
+  HIP_TRY(recs.ensure((size_t)std::max<int64_t>(entries, 1)));
+  HIP_TRY(var.ensure((size_t)var_bound));
+  KeySet ks;
+  memset(&ks, 0, sizeof(ks));
+  ks.n_keys = 1;
+  ks.null_as_group = mode;
+  ks.cols[0] = KeyCol{dphys.type, 0, dphys.validity, dphys.values, dphys.data};
+  if (entries) {
+    hipLaunchKernelGGL(freq_dict_records, dim3(grid_for((uint64_t)entries)), dim3(256), 0, st, ks,
+                       f->exact ? 1 : 0, entries, cnt.p, recs.p, var.p, words + 2);
+    HIP_TRY(hipGetLastError());
+  }
+  unsigned long long w[4] = {0, 0, 0, 0};
+  HIP_TRY(d2h(w, words + 2, sizeof(w), st));
+  int64_t special[3] = {0, 0, 0};
+  special[mode ? 1 : 2] = (int64_t)(h[1] + w[2]);
+  const int64_t rc[1] = {(int64_t)w[0]}, vb[1] = {(int64_t)w[1]};
+  const bool nan_counted = f->nan_counted;
+  const dq_status s = add_records(f, reinterpret_cast<const dq_freq_record*>(recs.p), var.p, 1, rc, vb, rows,
+                                  special, null_as_group, hip_stream, false);
+  if (s != DQ_OK) return s;
+  f->nan_counted = nan_counted;  // (this path counts the folded rows, as the row path does)
+  if (w[3]) {
+    f->h_counters[C_NAN_FOLDED] += w[3];
+    return push_counters(f);
+  }
+  return DQ_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Multi-GPU raw-key repartition: a one-column fixed-width key of high
 // cardinality (a unique id) is exchanged as its raw values, before any local count -- one
 // group-by per row on its owner rank and 1-8 bytes per row over xGMI, instead of a local group-by,

@@ -144,6 +144,16 @@ constexpr int kMaxStack = 16;
 // Arrow bitmap at a bit offset -> bitmap at bit 0 (cast.hip; sliced Arrow arrays at the ABI).
 hipError_t launch_bitmap_rebase(const uint8_t* src, int64_t bit, int64_t rows, uint8_t* dst,
                                 hipStream_t stream);
+// tiles[0 .. n) counts -> exclusive offsets in place, tiles[n] = the total: the single-block middle
+// launch of a three-launch scan (rowschema.hip; dq_select_plan, dq_gather_column, dq_dict_decode).
+hipError_t launch_tile_scan(uint32_t* tiles, int64_t n, hipStream_t stream);
+// Rows per dictionary entry (dict.hip): counts[entries] += the rows whose valid index names the
+// entry, words[0] += valid indices outside [0, entries) (never used as an address), words[1] +=
+// NULL indices.  index_type is a dq_index_type.
+bool dict_index_type_ok(int index_type);
+hipError_t launch_dict_count(const void* indices, int index_type, const uint8_t* valid, int64_t rows,
+                             int64_t entries, unsigned long long* counts, unsigned long long* words,
+                             hipStream_t stream);
 hipError_t launch_expr(const XInstr* prog, int n_instr, const DevCol* cols, const uint8_t* pool,
                        int64_t rows, uint64_t* out_val, uint64_t* out_vld, hipStream_t stream);
 // PatternMatch over a utf8 column with a fused automaton table (expr.hip): ns * 256 u8 successors

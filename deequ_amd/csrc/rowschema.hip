@@ -524,6 +524,12 @@ int fixed_width(int32_t type) {
 }
 
 }  // namespace
+
+hipError_t launch_tile_scan(uint32_t* tiles, int64_t n, hipStream_t stream) {
+  hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(kBlock), 0, stream, tiles, n);
+  return hipGetLastError();
+}
+
 }  // namespace dq
 
 using namespace dq;

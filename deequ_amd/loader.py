@@ -154,6 +154,8 @@ class HostTable:
         for f in schema:
             if f.type == pa.large_string():
                 raise TypeError(f"column {f.name}: large_string has 64-bit offsets")
+            if str(f.type) not in _ARROW_TO_DQ:
+                raise TypeError(f"unsupported Arrow type {f.type} for column {f.name}")
             fields.append(StructField(f.name, _ARROW_TO_DQ[str(f.type)]))
         out = [{f.name: ArrowColumn(rb.column(i)) for i, f in enumerate(fields)} for rb in batches]
         return HostTable(StructType(fields), out)

@@ -21,6 +21,11 @@ _ARROW_TO_DQ = {
     "float": N.FLOAT32, "double": N.FLOAT64, "string": N.UTF8, "large_string": N.UTF8,
     "binary": N.UTF8, "large_binary": N.UTF8, "date32[day]": N.DATE32,
 }
+# Arrow dictionary index types -> (dq_index_type, numpy type)
+_INDEX_TYPES = {"int8": (N.INDEX_INT8, np.int8), "uint8": (N.INDEX_UINT8, np.uint8),
+                "int16": (N.INDEX_INT16, np.int16), "uint16": (N.INDEX_UINT16, np.uint16),
+                "int32": (N.INDEX_INT32, np.int32), "uint32": (N.INDEX_UINT32, np.uint32),
+                "int64": (N.INDEX_INT64, np.int64), "uint64": (N.INDEX_UINT64, np.uint64)}
 _NP_OF = {N.INT8: np.int8, N.INT16: np.int16, N.INT32: np.int32, N.INT64: np.int64,
           N.FLOAT32: np.float32, N.FLOAT64: np.float64, N.DATE32: np.int32,
           N.TIMESTAMP_US: np.int64}
@@ -31,9 +36,17 @@ def arrow_field_type(t):
     of an Arrow type.  Spark's types map onto the engine's: binary is read as its bytes (hashed,
     grouped and matched exactly like a string, Spark's BinaryType), date64 as date32 days, a
     timestamp of any unit / zone as UTC microseconds (Spark's TimestampType), decimal128(p, s) as
-    itself.  Anything else (lists, structs, maps, decimal256, ...) is UNSUPPORTED: only its validity
+    itself.  dictionary<I, V> over any of these V is V's type (Spark has no dictionary type): the
+    column is imported decoded, and its batches keep the encoded pair beside it (EncodedColumn).
+    Anything else (lists, structs, maps, decimal256, ...) is UNSUPPORTED: only its validity
     bitmap reaches the device."""
     import pyarrow as pa
+    if pa.types.is_dictionary(t):
+        dtype, spark_name, as_type = arrow_field_type(t.value_type)
+        if (dtype == N.UNSUPPORTED or pa.types.is_dictionary(t.value_type)
+                or str(t.index_type) not in _INDEX_TYPES):
+            return N.UNSUPPORTED, None, t
+        return dtype, spark_name, pa.dictionary(t.index_type, as_type)
     key = str(t)
     if key in ("binary", "large_binary"):
         return N.UTF8, "BinaryType", pa.binary()
@@ -96,6 +109,27 @@ class StructType:
 
 
 @dataclass
+class EncodedColumn:
+    """The encoded pair of a dictionary column's batch: one index per row (any integer width, its
+    own validity) and the dictionary, an ordinary column.  A row is NULL when its index is NULL or
+    the entry it names is NULL.  The one-key frequency path counts the indices directly
+    (dq_freq_add_dict_device); everything else reads the decoded ColumnBatch that holds this."""
+    index_type: int             # dq_index_type
+    length: int
+    indices: object             # torch tensor of the index type's width
+    validity: Optional[object]  # torch.uint8 tensor or None
+    dictionary: "ColumnBatch"
+
+    def indices_c(self) -> N.dq_column:
+        c = N.dq_column()
+        c.type = 0  # (not read: index_type names the width)
+        c.length = self.length
+        c.validity = self.validity.data_ptr() if self.validity is not None else None
+        c.values = self.indices.data_ptr()
+        return c
+
+
+@dataclass
 class ColumnBatch:
     """One column of one record batch, as device buffers."""
     dtype: int
@@ -105,6 +139,7 @@ class ColumnBatch:
     data: Optional[object] = None  # torch.uint8 tensor (utf8 bytes)
     null_count: int = 0
     stand_in: bool = False  # an UNSUPPORTED column: validity only, `values` a 16-byte stand-in
+    encoded: Optional[EncodedColumn] = None  # a dictionary column's batch: what it was decoded from
 
     def to_c(self) -> N.dq_column:
         c = N.dq_column()
@@ -180,7 +215,13 @@ class Table:
         if max_batch_rows:
             batches = data.to_batches(max_chunksize=max_batch_rows)
         else:
-            batches = data.combine_chunks().to_batches() if data.num_rows else []
+            try:
+                batches = data.combine_chunks().to_batches() if data.num_rows else []
+            except pa.ArrowInvalid:
+                # chunks whose dictionaries Arrow cannot unify (NULL entries): one batch per chunk
+                if not any(pa.types.is_dictionary(f.type) for f in data.schema):
+                    raise
+                batches = data.to_batches()
         fields, casts = [], []
         for f in data.schema:
             dtype, spark_name, as_type = arrow_field_type(f.type)
@@ -189,9 +230,13 @@ class Table:
             casts.append(as_type if dtype != N.UNSUPPORTED and as_type != f.type else None)
         schema = StructType(fields)
         out = []
+        dictionaries: dict = {}  # uploaded dictionaries (batches cut from one chunk share theirs)
         for rb in batches:
             cols = {}
             for f, arr, cast in zip(fields, rb.columns, casts):
+                if f.dtype != N.UNSUPPORTED and pa.types.is_dictionary(arr.type):
+                    cols[f.name] = _dictionary_to_device(arr, f, cast, device, dictionaries)
+                    continue
                 if cast is not None:  # (exact: a cast that would drop digits raises)
                     arr = arr.cast(cast)
                 cols[f.name] = _array_to_device(arr, f.dtype, device)
@@ -314,3 +359,103 @@ def _array_to_device(arr, dtype: int, device: str) -> ColumnBatch:
                        _to_device(values, device),
                        _to_device(data, device) if data is not None else None, arr.null_count,
                        stand_in)
+
+
+def _dictionary_to_device(arr, field: StructField, cast, device: str, uploaded: dict) -> ColumnBatch:
+    """One batch of a dictionary<I, V> column: the decoded column (the layout _array_to_device gives
+    the decoded array), decoded on the device by dq_dict_decode, holding its encoded pair.  On the
+    host device ("cpu", no GPU) and for an empty batch: arr.dictionary_decode(), nothing kept."""
+    import pyarrow as pa
+    value_type = cast.value_type if cast is not None else arr.type.value_type
+    n = len(arr)
+    if str(device) == "cpu" or n == 0:
+        plain = arr.dictionary_decode()
+        if plain.type != value_type:
+            plain = plain.cast(value_type)
+        return _array_to_device(plain, field.dtype, device)
+    values = arr.dictionary
+    if len(values) >= 1 << 31:
+        raise TypeError(f"column {field.name}: a dictionary of {len(values)} entries (at most 2^31-1)")
+    key = (str(arr.type), values.offset, len(values),
+           tuple(b.address if b is not None else 0 for b in values.buffers()))
+    dictionary = uploaded.get(key)
+    if dictionary is None:
+        if values.type != value_type:
+            values = values.cast(value_type)
+        dictionary = uploaded[key] = _array_to_device(values, field.dtype, device)
+    index_type, npt = _INDEX_TYPES[str(arr.type.index_type)]
+    idx = arr.indices
+    bufs = idx.buffers()
+    validity = _bits(bufs[0], idx.offset, n) if idx.null_count else None
+    raw = np.frombuffer(bufs[1], dtype=npt)[idx.offset: idx.offset + n]
+    per16 = 16 // np.dtype(npt).itemsize
+    raw = np.concatenate([raw, np.zeros((-n) % per16 + per16, npt)])
+    enc = EncodedColumn(index_type, n, _to_device(raw.view(np.uint8), device),
+                        _to_device(validity, device) if validity is not None else None, dictionary)
+    return _decode_on_device(enc, field, device, arr)
+
+
+def _zeros(nbytes: int, device: str, npt=np.uint8):
+    import torch
+    t = N.retry_on_oom(torch.zeros, nbytes, dtype=torch.uint8, device=device)
+    return t if npt is np.uint8 else t.view(torch.from_numpy(np.zeros(0, npt)).dtype)
+
+
+def _decode_on_device(enc: EncodedColumn, field: StructField, device: str, arr) -> ColumnBatch:
+    """dq_dict_decode into buffers of exactly array_to_host's sizes and padding."""
+    import ctypes
+
+    import torch
+    dtype, n, d = field.dtype, enc.length, enc.dictionary
+    stream = ctypes.c_void_p(torch.cuda.current_stream(torch.device(device)).cuda_stream)
+    vbytes = (n + 7) // 8
+    with_validity = enc.validity is not None or d.validity is not None
+    validity = _zeros(vbytes + (-vbytes) % 16 + 16, device) if with_validity else None
+    data = None
+    cin, cdict = enc.indices_c(), d.to_c()
+    cout = N.dq_column()
+    cout.type = dtype
+    cout.length = n
+    cout.validity = validity.data_ptr() if validity is not None else None
+    bad = ctypes.c_int64()
+
+    def decode():
+        N.check(N.lib.dq_dict_decode(ctypes.byref(cin), enc.index_type, ctypes.byref(cdict),
+                                     ctypes.byref(cout), ctypes.byref(bad), stream))
+        if bad.value:
+            raise ValueError(f"column {field.name}: {bad.value} of {n} rows hold a dictionary index "
+                             f"outside [0, {d.length})")
+
+    if N.is_decimal(dtype):
+        values = _zeros(16 * n + 16, device, np.uint64)
+    elif dtype == N.BOOL:
+        values = _zeros(vbytes + (-vbytes) % 16 + 16, device)
+    elif dtype == N.UTF8:
+        values = _zeros(4 * (n + 1 + (-(n + 1)) % 4 + 4), device, np.int32)
+        decode()  # (data NULL: the string bytes the rows need)
+        nbytes = int(cout.data_bytes)
+        data = _zeros(nbytes + 16 + (-nbytes) % 16, device)
+        cout.data = data.data_ptr()
+        cout.data_bytes = nbytes
+    else:
+        npt = _NP_OF[dtype]
+        per16 = 16 // np.dtype(npt).itemsize
+        values = _zeros((n + (-n) % per16 + per16) * np.dtype(npt).itemsize, device, npt)
+    cout.values = values.data_ptr()
+    decode()
+    nulls = enc_null_count(arr)
+    if nulls == 0:
+        validity = None
+    return ColumnBatch(dtype, n, validity, values, data, nulls, False, enc)
+
+
+def enc_null_count(arr) -> int:
+    """NULL rows of a dictionary array whose indices are all in range: NULL indices plus the valid
+    indices that name a NULL entry."""
+    import pyarrow.compute as pc
+    idx, values = arr.indices, arr.dictionary
+    nulls = idx.null_count
+    if values.null_count and len(idx) > nulls:
+        hit = pc.sum(pc.take(values.is_null(), idx)).as_py()
+        nulls += int(hit or 0)
+    return nulls

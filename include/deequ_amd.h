@@ -662,6 +662,47 @@ dq_status dq_gather_column(const dq_column* in, const int32_t* index, int64_t n_
                            dq_column* out, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Dictionary-encoded columns (Arrow dictionary<I, V>): the dictionary is an ordinary dq_column of
+ * V; the indices travel as a dq_column whose `values` are `length` integers of the width and
+ * signedness index_type names (its `type` is not read) and whose `validity` is the indices'.  A
+ * row is NULL when its index is NULL or the entry it names is NULL.  Device memory throughout.
+ * ---------------------------------------------------------------------------------------------- */
+typedef enum dq_index_type {
+  DQ_INDEX_INT8 = 1, DQ_INDEX_UINT8 = 2, DQ_INDEX_INT16 = 3, DQ_INDEX_UINT16 = 4,
+  DQ_INDEX_INT32 = 5, DQ_INDEX_UINT32 = 6, DQ_INDEX_INT64 = 7, DQ_INDEX_UINT64 = 8
+} dq_index_type;
+
+/* Decodes the column into the caller's buffers named by `out`, under dq_gather_column's buffer
+ * contract: out->type equals dictionary->type, out->values holds `length` values (DQ_BOOL:
+ * (length + 7) / 8 bytes; DQ_UTF8: length + 1 int32 offsets starting at 0), out->data (DQ_UTF8)
+ * holds out->data_bytes bytes (DQ_ERR_INVALID_ARGUMENT when the strings need more); on return
+ * out->length = indices->length and out->data_bytes = the string bytes written.  Unlike
+ * dq_gather_column the indices have any width and signedness, their validity is honoured, and
+ * out->validity is (length + 7) / 8 LSB-first bytes, one per 8 rows (it may be NULL only when
+ * neither the indices nor the dictionary have a validity bitmap).  A DQ_UTF8 call with
+ * out->data == NULL writes nothing and returns the string bytes needed in out->data_bytes.
+ * *n_bad_index counts the rows whose valid index is negative or >= dictionary->length: such a
+ * row is written as NULL / zero / empty, and no address is formed from its index.  More than
+ * 2^31-1 decoded string bytes (int32 offsets): DQ_ERR_UNSUPPORTED.  Fixed-width values: one launch;
+ * utf8: lengths and validity, an exclusive scan, the byte copy -- no workgroup waits for another.
+ * Synchronises `hip_stream`. */
+dq_status dq_dict_decode(const dq_column* indices, int index_type, const dq_column* dictionary,
+                         dq_column* out, int64_t* n_bad_index, void* hip_stream);
+
+/* dq_freq_add_device for a one-key table and a dictionary-encoded key column, without decoding
+ * it: the rows are counted per dictionary entry, and one (key, count) record per used non-NULL
+ * entry goes through dq_freq_add_records_device's insert path, so every entry is hashed and
+ * encoded once, not once per row.  Afterwards the table's observable state (dq_freq_export as a
+ * set, dq_freq_summarize, dq_freq_topk counts, dq_freq_null_literal, dq_freq_num_rows,
+ * dq_freq_folded_nan_rows) is what dq_freq_add_device over the decoded batch leaves: NULL rows go
+ * to the skipped count or the NULL group as null_as_group says, duplicate entries fall into one
+ * group, NaN payloads are canonical under null_as_group.  dictionary->type is the table's key type.
+ * A valid index outside [0, dictionary->length) fails the call with DQ_ERR_INVALID_ARGUMENT and
+ * leaves the table as it was.  Waits for `hip_stream`. */
+dq_status dq_freq_add_dict_device(dq_freq* freq, const dq_column* indices, int index_type,
+                                  const dq_column* dictionary, int null_as_group, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Columnar handoff: host-resident Arrow batches -> HBM (the JNI shim's entry).
  *
  * In the reference a Spark partition's rows stream through the aggregation iterator of the one

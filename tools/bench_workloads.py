@@ -28,7 +28,13 @@ configs[1], S10).  Not part of the driver's bench contract; the JSON lines land 
       rank, each rank's ms per step, and each rank's collective bytes per step (run_distributed).
   --cpu-baseline: the C/OpenMP restatement (oracle/oracle.c) timed on a bounded sample.
 
-Usage: python tools/bench_workloads.py c3|c4|c5 [--rows N] [--steps K] [--warmup W] [--gpus N]
+  dict: Histogram + Uniqueness + Entropy (through AnalysisRunner) on a synthetic 3-value `priority`
+      column, once as a plain string column and once dictionary-encoded with int8 indices
+      (dq_freq_add_dict_device), same build, same process, same rows.  The comparison is the
+      string path.  B_alg: string = validity + offsets + bytes, encoded = validity + one index
+      byte (1.125 B/row).
+
+Usage: python tools/bench_workloads.py c3|c4|c5|dict [--rows N] [--steps K] [--warmup W] [--gpus N]
        [--cpu-baseline]
 """
 import argparse
@@ -45,7 +51,7 @@ PEAK = 8.0e12
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("workload", choices=["c3", "c4", "c5"])
+    ap.add_argument("workload", choices=["c3", "c4", "c5", "dict"])
     ap.add_argument("--rows", type=int, default=0)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
@@ -79,13 +85,62 @@ def main():
     if world > 1:
         return run_distributed(args, world, rank, local)
     rows = args.rows or DEFAULT_ROWS[args.workload]
+    if args.workload == "dict":
+        print(json.dumps(run_dict(rows, args.steps, args.warmup, min(args.batch_rows, 1 << 25))),
+              flush=True)
+        return
     out = run_single(args.workload, rows, args.steps, args.warmup, args.batch_rows,
                      runner=args.runner, pyprof=args.pyprof, verbose=True,
                      cpu_rows=args.cpu_rows if args.cpu_baseline else None)
     print(json.dumps(out), flush=True)
 
 
-DEFAULT_ROWS = {"c3": 1_000_000_000, "c4": 1_250_000_000, "c5": 125_000_000}
+DEFAULT_ROWS = {"c3": 1_000_000_000, "c4": 1_250_000_000, "c5": 125_000_000, "dict": 100_000_000}
+
+
+def run_dict(rows: int, steps: int, warmup: int, batch_rows: int, dev: str = "cuda:0") -> dict:
+    """The `dict` leg: the same three analyzers over the same 3-value column as a string column and
+    as a dictionary<int8, string> column.  Each step is one do_analysis_run between two device
+    syncs (wall clock); the first `warmup` steps of each leg are untimed; median and minimum of
+    the timed steps are reported, both legs from this one process."""
+    import numpy as np
+    import pyarrow as pa
+    import torch
+
+    from deequ_amd import Table
+    from deequ_amd.analyzers import Entropy, Histogram, Uniqueness
+    from deequ_amd.runners import AnalysisRunner
+    rng = np.random.default_rng(9)
+    idx = pa.array(rng.integers(0, 3, rows).astype(np.int8), mask=rng.random(rows) < 0.05)
+    enc = pa.DictionaryArray.from_arrays(idx, pa.array(["high", "low", "medium"]))
+    suite = [Histogram("priority"), Uniqueness(["priority"]), Entropy("priority")]
+    out = {"workload": "dict", "rows": rows, "steps": steps, "warmup": warmup}
+    values = {}
+    for leg, col in (("string", None), ("encoded", enc)):
+        if col is None:  # (chunked: int32 offsets hold one batch's bytes, not the column's)
+            col = pa.chunked_array([enc.slice(o, batch_rows).dictionary_decode()
+                                    for o in range(0, rows, batch_rows)])
+        table = Table.from_arrow(pa.table({"priority": col}), device=dev, max_batch_rows=batch_rows)
+        key_bytes = sum(b["priority"].nbytes() if leg == "string" else
+                        b["priority"].encoded.indices.numel() + (b["priority"].length + 7) // 8
+                        for b in table.batches)
+        ms = []
+        for k in range(warmup + steps):
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            ctx = AnalysisRunner.do_analysis_run(table, suite)
+            torch.cuda.synchronize(dev)
+            if k >= warmup:
+                ms.append((time.perf_counter() - t0) * 1e3)
+        values[leg] = [str(ctx.metric(a).value.get()) for a in suite]
+        ms.sort()
+        out[leg] = {"ms_median": ms[len(ms) // 2], "ms_min": ms[0], "ms_all": ms,
+                    "key_bytes_per_row": key_bytes / rows, "batches": len(table.batches)}
+        del table, ctx
+        torch.cuda.empty_cache()
+    out["same_metrics"] = values["string"] == values["encoded"]
+    out["string_over_encoded"] = out["string"]["ms_median"] / out["encoded"]["ms_median"]
+    return out
 
 
 def run_single(workload: str, rows: int, steps: int, warmup: int, batch_rows: int = 1 << 26,
