@@ -42,209 +42,11 @@
 // 64-bit collision never merges groups.  Counts of equal keys are SUMMED in every pass, which is
 // also what FrequenciesAndNumRows.sum (GroupingAnalyzers.scala:128-148) needs: merging two tables
 // appends one's chunks to the other's.
-#include <hip/hip_runtime.h>
-
-#include <type_traits>
-
-#include <algorithm>
-#include <chrono>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <array>
-#include <map>
-#include <mutex>
-#include <vector>
-
-#include "engine.h"
-#include "freq_codec.h"
-#include "kernels.h"
-#include "stream_load.h"
+//
+// The table itself (struct dq_freq) and the file map are in freq_table.h.
+#include "freq_table.h"
 
 namespace dq {
-
-#define DQ_DEV __device__ __forceinline__
-
-constexpr int kBucketBits = 9;
-constexpr int kBuckets = 1 << kBucketBits;
-constexpr int kHistRow = kBuckets + 1;  // u16 exclusive bucket prefix of a chunk + its total
-constexpr int kThreads = 1024;
-constexpr int kMaxSubBits = 10;
-constexpr int kMinPkSubBits = 7;  // packed phase-C slots need a partition of >= 9 + 7 fixed bits
-constexpr int kFilterShift = 32;        // hash bits that split an overflowing partition
-constexpr int kCand = 4;                // top groups kept per partition for Histogram
-constexpr int kSmallCounts = 64;        // phase C histograms group counts below this
-constexpr int kMaxParts = 64;
-constexpr uint64_t kEmptyKey = ~0ULL;
-constexpr uint64_t kNotReady = ~0ULL;
-
-// C_MAXCNT: an upper bound of the count any phase-A record carries (packed phase-C slots at
-// fewer than kMaxSubBits sub-bits need every record count below 2^(s-3); merges add the bounds)
-// C_NAN_FOLDED: keyed rows of a Histogram-mode floating-point table whose NaN payload was folded
-// into the canonical NaN (zero: the table's groups are also the grouping's, dq_freq_folded_nan_rows)
-enum Counter { C_NULL_ROWS = 0, C_NULL_GROUP, C_COLLISIONS, C_DBG_NOTREADY, C_DBG_DIFF, C_DBG_FULL, C_DBG_BYPASS,
-               C_MAXCNT, C_NAN_FOLDED, C_N };
-
-template <bool HASHED>
-struct FM;
-template <>
-struct FM<false> {
-  static constexpr int kTile = 8192;    // rows (and at most records) per phase-A chunk
-  static constexpr int kRB = 8;         // bytes per record
-  static constexpr int kTableC = 4096;  // phase-C LDS table slots (two workgroups per CU)
-  static constexpr int kTarget = 2000;  // records per final partition the sizing aims at
-  // records per partition of a table one level shallower that stays packed (finalize_b)
-  static constexpr uint64_t kTargetPk = 3700;
-};
-template <>
-struct FM<true> {
-  static constexpr int kTile = 2048;
-  static constexpr int kRB = 16;
-  static constexpr int kTableC = 2560;
-  // (freq_phaseC_h takes up to 4096 records and 3584 groups per partition: ~1900-record partitions
-  // halve its per-item costs against ~950, configs[4] 176.3 -> 171.5 ms)
-  static constexpr int kTarget = 2400;
-};
-// records per phase-B unit (whole chunk segments of one bucket): hashed two tiles (~32 records per
-// partition run); exact one (8192 records: the whole-unit scatter then stages 64 KB and two
-// workgroups share a CU, configs[2] 26.3 -> 25.0 ms)
-constexpr int kUnitTilesH = 2, kUnitTilesX = 1;
-
-struct RecIn {  // == dq_freq_record
-  uint64_t key;
-  uint64_t count;
-  uint64_t enc_off;
-};
-
-struct Group {  // one materialised group
-  uint64_t h;
-  uint64_t count;
-  uint64_t rep;  // hashed: arena offset of the encoded key
-};
-
-struct FEntry {  // phase-C work item of a recount: partition p, hash subset v of 2^f
-  uint32_t p, f, v, pad;
-};
-
-struct SrcSegs {
-  int64_t rec_start[kMaxParts + 1];
-  int64_t var_base[kMaxParts];
-  int32_t n_src;
-};
-
-// ------------------------------------------------------------------------------------------------
-// Device helpers
-// ------------------------------------------------------------------------------------------------
-DQ_DEV uint64_t lds_load(const uint64_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-DQ_DEV void lds_store(uint64_t* p, uint64_t v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// ockl wavefront reductions / scans: DPP row and broadcast steps, no LDS round trips (the
-// __shfl_* forms are ds_bpermute, a few hundred cycles for a 6-step 64-bit chain)
-extern "C" __device__ uint32_t __ockl_wfred_add_u32(uint32_t);
-extern "C" __device__ uint64_t __ockl_wfred_add_u64(uint64_t);
-extern "C" __device__ double __ockl_wfred_add_f64(double);
-extern "C" __device__ uint64_t __ockl_wfred_max_u64(uint64_t);
-extern "C" __device__ uint32_t __ockl_wfscan_add_u32(uint32_t, bool);
-
-// Exclusive scan of one u32 per thread over the workgroup; returns the thread's prefix and sets
-// `total`.  Every thread of the block must call it.
-DQ_DEV uint32_t block_excl_scan(uint32_t v, uint32_t* s_wave, uint32_t& total) {
-  const int lane = __lane_id(), wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  const uint32_t x = __ockl_wfscan_add_u32(v, true);
-  if (lane == 63) s_wave[wave] = x;
-  __syncthreads();
-  if (wave == 0) {
-    const uint32_t w = __ockl_wfscan_add_u32(lane < nw ? s_wave[lane] : 0u, true);
-    if (lane < nw) s_wave[lane] = w;
-  }
-  __syncthreads();
-  const uint32_t base = wave ? s_wave[wave - 1] : 0u;
-  total = s_wave[nw - 1];
-  __syncthreads();
-  return base + x - v;
-}
-
-template <typename T>
-DQ_DEV T wave_sum(T v) {
-  if constexpr (std::is_same_v<T, double>) return __ockl_wfred_add_f64(v);
-  else if constexpr (sizeof(T) == 8) return (T)__ockl_wfred_add_u64((uint64_t)v);
-  else return (T)__ockl_wfred_add_u32((uint32_t)v);
-}
-
-// Fixed-order block sums (every thread calls; the result is valid in every thread).
-DQ_DEV uint64_t block_sum_u64(uint64_t v, uint64_t* s) {
-  v = wave_sum(v);
-  const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  if (__lane_id() == 0) s[wave] = v;
-  __syncthreads();
-  uint64_t t = 0;
-  for (int w = 0; w < nw; ++w) t += s[w];
-  __syncthreads();
-  return t;
-}
-DQ_DEV double block_sum_f64(double v, double* s) {
-  v = wave_sum(v);
-  const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  if (__lane_id() == 0) s[wave] = v;
-  __syncthreads();
-  double t = 0.0;
-  for (int w = 0; w < nw; ++w) t += s[w];
-  __syncthreads();
-  return t;
-}
-
-// Sum over the wave, added to a table counter by lane 0 (counters are single addresses).
-DQ_DEV void wave_count(unsigned long long* counter, unsigned long long v) {
-  v = wave_sum(v);
-  if (__lane_id() == 0 && v) atomicAdd(counter, v);
-}
-extern "C" __device__ uint64_t __ockl_wfred_max_u64(uint64_t);
-// A workgroup's largest record count into an LDS word, only when it could bar packed slots
-// (>= 16 = 2^(7-3)); the workgroup then makes one global atomic (one per wave on one address
-// serialised phase A over records: 9.4 -> 50 ms per configs[4] run)
-DQ_DEV void wave_max_lds(unsigned long long* s_slot, uint64_t v) {
-  v = __ockl_wfred_max_u64(v);
-  if (__lane_id() == 0 && v >= 16) atomicMax(s_slot, (unsigned long long)v);
-}
-
-// last index j in [0, n) with pos[j] <= x (pos non-decreasing, pos[0] = 0 <= x)
-DQ_DEV uint32_t seg_of(const uint32_t* pos, uint32_t n, uint32_t x) {
-  uint32_t lo = 0, hi = n;  // answer in [lo, hi)
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (pos[mid] <= x) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
-DQ_DEV int64_t seg_var_base(const SrcSegs& s, int64_t i) {
-  int j = 0;
-  while (j + 1 < s.n_src && i >= s.rec_start[j + 1]) ++j;
-  return s.var_base[j];
-}
-
-template <typename F>
-DQ_DEV void for_digits(uint64_t c, F&& f) {
-  for (uint32_t e = 0; c; c >>= 2, ++e)
-    if (c & 3) f((e << 2) | (uint32_t)(c & 3));
-}
-
-DQ_DEV uint32_t bucket_of(uint64_t h) { return (uint32_t)(h >> (64 - kBucketBits)); }
-// sub-bucket (the s hash bits below the bucket bits); x = h or the exact record >> 8 (both hold
-// hash bits 54..0 in place)
-DQ_DEV uint32_t sub_of(uint64_t x, int s) {
-  return s ? (uint32_t)((x >> (64 - kBucketBits - s)) & ((1u << s) - 1u)) : 0u;
-}
-DQ_DEV uint64_t xrec_h(uint64_t rec, uint32_t b) {
-  return ((uint64_t)b << 55) | ((rec >> 8) & ((1ULL << 55) - 1));
-}
 
 // ------------------------------------------------------------------------------------------------
 // Phase A: rows (or received records) -> bucket-sorted chunk regions
@@ -2708,58 +2510,6 @@ DQ_DEV void c_fetch(const CArgs& a, int wi, const CBounds& bd, CItem<HASHED>& it
   }
 }
 
-// -(c/n) ln(c/n), out of line: the statistics pass calls it from every unrolled slot, and inlined
-// copies of log() there made phase C several times larger than the instruction cache holds
-__device__ __attribute__((noinline)) double entropy_term(uint64_t c, double n) {
-  const double pr = (double)c / n;
-  return -pr * log(pr);
-}
-
-// ---- Exact sums of fp64 terms (Entropy's -p ln p, MutualInformation's p ln(p / (px py))) ----
-// A term enters as a signed 128-bit fixed-point integer at 2^-112 (exact for every term of
-// magnitude >= 2^-60, cut below 2^-112), so a sum is the same integer in ANY order: the table's
-// entropy is the sum of its groups' terms whatever the phase-C insert order, the partition depth,
-// the recount subsets or the order partial sums meet in -- bit-stable from run to run.  Terms are
-// bounded (|term| <= ln(rows) < 2^6), sums stay far inside 2^15.
-using fix128 = __int128;
-constexpr double kFixUlp = 0x1p-112;
-DQ_HD fix128 fix_of(double x) {
-  const uint64_t b = __builtin_bit_cast(uint64_t, x);
-  const int ex = (int)((b >> 52) & 0x7ff);
-  if (ex == 0) return 0;  // zero (and subnormals, < 2^-1022: cut)
-  const uint64_t m = (b & ((1ULL << 52) - 1)) | (1ULL << 52);
-  const int sh = ex - 1075 + 112;  // x = m 2^(ex - 1075); fixed = m 2^(ex - 1075 + 112)
-  const fix128 v = sh >= 0 ? ((fix128)m << sh) : (sh > -64 ? (fix128)(m >> -sh) : (fix128)0);
-  return (b >> 63) ? -v : v;
-}
-// (a fixed sequence of roundings: deterministic, within 2 ulp)
-DQ_HD double fix_to_f64(fix128 v) {
-  const int64_t hi = (int64_t)(v >> 64);
-  const uint64_t lo = (uint64_t)v;
-  return ((double)hi * 18446744073709551616.0 + (double)lo) * kFixUlp;
-}
-DQ_DEV fix128 wave_sum_fix(fix128 v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) {
-    const uint64_t lo = __shfl_xor((unsigned long long)(uint64_t)v, o);
-    const uint64_t hi = __shfl_xor((unsigned long long)(uint64_t)(v >> 64), o);
-    v += (fix128)(((unsigned __int128)hi << 64) | lo);
-  }
-  return v;
-}
-// p[0..1] += v (lo, hi words): the carry of each lo add goes with that add's hi, so the total is
-// exact whatever order the adds land in
-DQ_DEV void atomic_add_fix(unsigned long long* p, fix128 v) {
-  const uint64_t lo = (uint64_t)v, hi = (uint64_t)(v >> 64);
-  const uint64_t old = atomicAdd(p, (unsigned long long)lo);
-  const uint64_t up = hi + (old + lo < old ? 1u : 0u);
-  if (up) atomicAdd(p + 1, (unsigned long long)up);
-}
-DQ_DEV void store_fix(unsigned long long* p, fix128 v) {
-  p[0] = (uint64_t)v;
-  p[1] = (uint64_t)(v >> 64);
-}
-
 // Hashed tables' recount rounds (a hashed first pass is freq_phaseC_h, exact tables run
 // freq_phaseC_x).  Per work item: the inserts, then ONE pass over the LDS table that reads every slot once for
 // the statistics, the Histogram candidates (kept in registers) and the lit probe, and clears it
@@ -4368,14 +4118,6 @@ __global__ void freq_cand_clear(Group* cand, const FEntry* list, int64_t n) {
   if (i < n * kCand) cand[(uint64_t)list[i / kCand].p * kCand + i % kCand] = Group{0, 0, 0};
 }
 
-struct PartTypes {
-  int32_t types[kMaxKeys];
-  int32_t n_keys;
-  int32_t exact;
-  uint32_t parts;
-  uint32_t pad;
-};
-
 // Owner rank of a group for the multi-GPU repartition: the high hash bits, so every owner gets a
 // contiguous hash range (and the owner's own partitions stay uniformly loaded).
 DQ_DEV uint32_t owner_of(uint64_t h, uint32_t parts) {
@@ -4473,6 +4215,55 @@ __global__ void freq_compact(const Group* src, const unsigned long long* src_off
 }
 
 
+// decimal keys (physical_keys): decimal(p <= 18) narrowed to its unscaled long; decimal(p > 18)'s
+// string offsets 0, 16, 32, ...
+__global__ void dec_narrow_kernel(const uint64_t* __restrict__ in, int64_t* __restrict__ out,
+                                  int64_t rows) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < rows;
+       i += (int64_t)gridDim.x * blockDim.x)
+    out[i] = (int64_t)in[2 * i];
+}
+__global__ void iota16_kernel(int32_t* __restrict__ out, int64_t n) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x)
+    out[i] = (int32_t)(16 * i);
+}
+
+// Dictionary-encoded batches (dq_freq_add_dict_device): one record per used entry.
+// words: [0] records written, [1] var bytes written, [2] rows of NULL entries, [3] rows whose NaN
+// payload the Histogram mode folded (C_NAN_FOLDED, as the row path counts it)
+__global__ void __launch_bounds__(256)
+freq_dict_records(KeySet ks, int exact, int64_t entries, const unsigned long long* __restrict__ counts,
+                  RecIn* __restrict__ recs, uint8_t* __restrict__ var,
+                  unsigned long long* __restrict__ words) {
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < entries; e += (int64_t)gridDim.x * 256) {
+    const unsigned long long c = counts[e];
+    if (!c) continue;
+    if (!kbit(ks.cols[0].valid, e)) {
+      atomicAdd(words + 2, c);
+      continue;
+    }
+    RecIn r;
+    r.count = c;
+    r.enc_off = 0;
+    if (exact) {
+      const uint64_t raw = kwiden(ks.cols[0].type, ks.cols[0].values, e);
+      r.key = exact_canon(ks, raw);
+      if (r.key != raw) atomicAdd(words + 3, c);
+    } else {  // (one key and hashed: a utf8 key)
+      const SView v = str1_view(ks, e);
+      const uint32_t enc = str1_enc_size(ks, e), sz = (enc + 7u) & ~7u;
+      const unsigned long long at = atomicAdd(words + 1, (unsigned long long)sz);
+      uint32_t* dst = reinterpret_cast<uint32_t*>(var + at);
+      str1_encode(ks, e, dst);
+      if (sz != enc) dst[enc / 4] = 0;
+      r.key = str_row_hash(v);
+      r.enc_off = at;
+    }
+    recs[atomicAdd(words, 1ull)] = r;
+  }
+}
+
 }  // namespace dq
 
 using namespace dq;
@@ -4480,233 +4271,6 @@ using namespace dq;
 // ------------------------------------------------------------------------------------------------
 // Host side
 // ------------------------------------------------------------------------------------------------
-
-// 8-byte page-locked words (the small-key phase A's give-up flag) carved from shared 4 KB blocks
-// kept to process exit: a hipHostMalloc + hipHostFree per table cost ~0.1-0.2 ms each at every
-// string Histogram job's boundary.
-struct PinnedWords {
-  std::mutex m;
-  std::vector<unsigned long long*> free_words;
-};
-static PinnedWords& pinned_words() {
-  static PinnedWords* w = new PinnedWords;
-  return *w;
-}
-static hipError_t pinned_word_get(unsigned long long** out) {
-  PinnedWords& w = pinned_words();
-  std::lock_guard<std::mutex> lock(w.m);
-  if (w.free_words.empty()) {
-    void* blk = nullptr;
-    hipError_t e = hipHostMalloc(&blk, 4096, hipHostMallocDefault);
-    if (e != hipSuccess) return e;
-    for (int i = 0; i < 512; ++i) w.free_words.push_back(static_cast<unsigned long long*>(blk) + i);
-  }
-  *out = w.free_words.back();
-  w.free_words.pop_back();
-  return hipSuccess;
-}
-// The caller has synchronized the stream of the last copy into the word (dq_freq_destroy), so
-// no copy can still land in it; no device-wide barrier (it would wait for other tables' streams).
-static void pinned_word_put(unsigned long long* p) {
-  PinnedWords& w = pinned_words();
-  std::lock_guard<std::mutex> lock(w.m);
-  w.free_words.push_back(p);
-}
-
-struct dq_freq {
-  int device = 0;
-  int n_keys = 0;
-  // key types as the caller declared them, and the physical layout the group-by runs on
-  // (freq_phys_type: dates / timestamps as their integers, decimals as their unscaled long or
-  // 16-byte string); every kernel below sees only `types`
-  std::vector<int32_t> logical;
-  std::vector<int32_t> types;
-  bool relabel = false;  // some logical type differs from its physical one
-  DevBuf<int64_t> dec_long[kMaxKeys];  // decimal(p <= 18) keys narrowed to their unscaled long
-  DevBuf<int32_t> dec_off;             // decimal(p > 18) keys: offsets 0, 16, 32, ... (shared)
-  bool exact = false;
-  int mode_null_as_group = -1;  // fixed by the first add
-  int tile = 0, rb = 0;
-  // the table: bucket-sorted chunk regions (phase A output) + their histograms
-  DevBuf<uint8_t> recs;
-  DevBuf<uint16_t> hist;
-  int64_t n_chunks = 0;
-  // exact rows: batch regions written bucket-major (freq_prepass_x), one piece row per phase-A
-  // workgroup: piece (r, b) = records [pbase[r] + pstart[r][b], + plen[r][b]) of `recs`
-  DevBuf<uint32_t> pstart, plen;
-  std::vector<unsigned long long> h_pbase;
-  int64_t n_prow = 0;
-  int64_t n_empty_chunks = 0;  // chunk rows known empty (bucket-piece batches): finalize skips them
-  DevBuf<uint32_t> ph, ptot;  // the pre-pass's per-workgroup bucket counts (scratch)
-  DevBuf<unsigned long long> pbase;
-  DevBuf<uint8_t> arena;                 // hashed: encoded keys
-  DevBuf<unsigned long long> dev_words;  // counters[C_N], then the arena cursor
-  DevBuf<unsigned long long> batch_tab;  // freq_phaseA_small's cross-workgroup group table
-  uint64_t h_counters[C_N] = {0};
-  uint64_t arena_used = 0;
-  uint64_t rec_var_base = 0;  // arena offset of the last dq_freq_add_records_device's var bytes
-  // a table built from another table's records may read that table's arena in place instead of
-  // a copy (MutualInformation's marginals, which die before their joint table): then the keys live
-  // here and the table takes no further adds
-  const uint8_t* arena_view = nullptr;
-  // phase A launches leave the device counters and arena cursor ahead of the host copies: they
-  // are read back only when needed (finalize, merge, arena growth), so batches queue back to back
-  bool counters_stale = false;
-  uint64_t arena_hi = 0;  // upper bound of the arena bytes in use (arena_used at the last read-back
-                          // + the worst case of every batch added since)
-  int64_t num_rows = 0;
-  hipStream_t stream = nullptr;
-  // the small-key phase A (freq_phaseA_small): the epoch of its last attempt, and a pinned copy of
-  // the epoch it last gave up (copied back asynchronously: a table it gave up on stops trying)
-  uint64_t fast_epoch = 0;
-  bool fast_off = false;
-  // every batch went through freq_phaseA_xp, which counts C_NAN_FOLDED (records, merges and the
-  // other phase-A kernels do not)
-  bool nan_counted = true;
-  struct PinnedWord {
-    unsigned long long* p = nullptr;
-    hipStream_t last_copy = nullptr;  // the stream of the last copy into *p
-    // Before a copy into *p is queued on `st`: a copy still queued on another stream could land
-    // after it (and after dq_freq_destroy synced only `st`, recycling the word to another table),
-    // so that stream is waited for first.  Same stream: stream order already holds.
-    hipError_t before_copy(hipStream_t st) {
-      hipError_t e = hipSuccess;
-      if (last_copy && last_copy != st) e = hipStreamSynchronize(last_copy);
-      last_copy = st;
-      return e;
-    }
-    ~PinnedWord() {
-      if (p) pinned_word_put(p);
-    }
-  } fast_seen;
-  // the dense integer path (freq_dense_count / _emit): its device words (AArgs::dense_words), the
-  // epoch of its last attempt, the counting workgroups' counters, and a pinned copy of the epoch
-  // it last declined (a table it declined stops trying)
-  DevBuf<unsigned long long> dense_words;
-  DevBuf<uint32_t> dense_part;
-  uint64_t dense_epoch = 0;
-  bool dense_off = false;
-  PinnedWord dense_seen;
-  // recorded behind the first tried batch's decline-word copy (ahead of its phase A): the second
-  // batch waits for that answer instead of trying again (a fresh table per run -- the runner's
-  // Histogram tables -- ran the range pre-pass on three or four batches of a wide column)
-  hipEvent_t dense_ev = nullptr;
-  bool dense_waited = false;
-  // finalize cache (phase B)
-  bool b_valid = false;
-  int s_bits = 0;
-  uint64_t R = 0;
-  uint32_t n_units = 0;
-  std::vector<unsigned long long> h_bucket_base = std::vector<unsigned long long>(kBuckets + 1, 0);
-  std::vector<uint32_t> h_unit_start = std::vector<uint32_t>(kBuckets + 1, 0);
-  DevBuf<unsigned long long> segS;         // phase B's segments per bucket (freq_seg_scan)
-  DevBuf<uint32_t> segP, nseg;
-  DevBuf<uint32_t> chunk_id;               // the non-empty chunks (finalize over those only)
-  DevBuf<unsigned long long> chunk_boff, scan_tmp;
-  DevBuf<uint32_t> unit_start, unit_c0, uhist;
-  DevBuf<uint16_t> unit_b;
-  DevBuf<unsigned long long> totals, part_base;
-  // Capacity layout (exact tables, finalize_b): partition p's records are [part_base[p],
-  // part_end[p]) inside a fixed capacity, filled through atomic cursors (no count pass).  The
-  // counted layout's ends are part_base + 1.  Rcap: the records region's size in records.
-  DevBuf<unsigned long long> part_end, cap_words;  // cap_words: bucket bases [kBuckets + 1], caps
-  DevBuf<unsigned int> b_ovf;
-  std::vector<unsigned long long> h_cap_words;
-  const unsigned long long* part_end_ptr = nullptr;
-  uint64_t Rcap = 0;
-  bool cap_failed = false;  // a capacity layout overflowed: this table counts from now on
-  DevBuf<uint8_t> recsB;
-  // (phase C)
-  bool c_valid = false, c_groups = false, c_cand = false;
-  double c_num_rows = -1.0;
-  DevBuf<unsigned long long> part_groups, part_unique, part_off;
-  DevBuf<unsigned long long> part_entropy;  // (lo, hi) fixed-point sum per partition
-  DevBuf<Group> cand, groups, compact;
-  int64_t n_compact = -1;
-  DevBuf<FEntry> ovf_a, ovf_b;
-  DevBuf<unsigned int> ovf_n;
-  DevBuf<unsigned long long> red;
-  uint64_t st_groups = 0, st_unique = 0;
-  double st_entropy = 0.0;
-  fix128 st_entropy_fix = 0;  // the same sum, before its rounding to fp64
-  uint64_t st_literal = 0;  // Histogram on a string: count of the "NullValue" string group
-  bool recounted = false;
-  // last top-k (dq_freq_topk is called twice: sizes, then data)
-  int topk_k = -1;
-  std::vector<int64_t> topk_counts, topk_offs;
-  std::vector<uint8_t> topk_bytes;
-};
-
-static unsigned grid_for(uint64_t n, unsigned cap = 4096) {
-  uint64_t g = (n + 255) / 256;
-  if (g < 1) g = 1;
-  if (g > cap) g = cap;
-  return (unsigned)g;
-}
-
-// A Histogram table over one string column: its NULL rows are kept apart from a "NullValue"
-// string group that phase C probes for.
-static bool has_null_literal(const dq_freq* f) {
-  return !f->exact && f->n_keys == 1 && f->types[0] == DQ_UTF8 && f->mode_null_as_group > 0;
-}
-
-static void invalidate(dq_freq* f) {
-  f->b_valid = false;
-  f->c_valid = f->c_groups = f->c_cand = false;
-  f->n_compact = -1;
-  f->topk_k = -1;
-}
-
-// Grows `b` to at least `need` elements keeping the first `used` (stream-ordered copy).
-template <typename T>
-static hipError_t grow_keep(DevBuf<T>& b, size_t used, size_t need, hipStream_t st) {
-  if (need <= b.n && b.p) return hipSuccess;
-  DevBuf<T> nb;
-  hipError_t e = nb.ensure(std::max(need, b.n * 2));
-  if (e != hipSuccess) return e;
-  if (used) {
-    e = hipMemcpyAsync(nb.p, b.p, used * sizeof(T), hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) return e;
-    e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return e;
-  }
-  b.swap(nb);
-  return hipSuccess;
-}
-
-static dq_status ensure_chunks(dq_freq* f, int64_t add) {
-  const int64_t need = f->n_chunks + add;
-  HIP_TRY(grow_keep(f->recs, (size_t)f->n_chunks * f->tile * f->rb, (size_t)need * f->tile * f->rb,
-                    f->stream));
-  HIP_TRY(grow_keep(f->hist, (size_t)f->n_chunks * kHistRow, (size_t)need * kHistRow, f->stream));
-  return DQ_OK;
-}
-
-// the counters and the arena cursor as read back (dev_words: C_N counters + the cursor)
-static void apply_counters(dq_freq* f, const unsigned long long* w) {
-  for (int k = 0; k < C_N; ++k) f->h_counters[k] = w[k];
-  f->arena_used = w[C_N];
-  f->arena_hi = f->arena_used;
-  f->counters_stale = false;
-}
-static dq_status pull_counters(dq_freq* f) {  // (d2h is ordered after the stream's work)
-  unsigned long long w[C_N + 1];
-  HIP_TRY(d2h(w, f->dev_words.p, sizeof(w), f->stream));
-  apply_counters(f, w);
-  return DQ_OK;
-}
-static dq_status sync_counters(dq_freq* f) { return f->counters_stale ? pull_counters(f) : DQ_OK; }
-
-static dq_status push_counters(dq_freq* f) {
-  HIP_TRY(hipStreamSynchronize(f->stream));
-  unsigned long long w[C_N + 1];
-  for (int k = 0; k < C_N; ++k) w[k] = f->h_counters[k];
-  w[C_N] = f->arena_used;
-  HIP_TRY(hipMemcpy(f->dev_words.p, w, sizeof(w), hipMemcpyHostToDevice));
-  f->arena_hi = f->arena_used;
-  f->counters_stale = false;
-  return DQ_OK;
-}
 
 // Chunks one phase-A launch over n items writes: one per tile + one per workgroup.
 static int64_t phaseA_chunks(bool hashed, bool from_rec, int64_t n_items, int64_t tile_items,
@@ -4724,12 +4288,8 @@ static void launch_phaseA(dq_freq* f, AArgs a, bool from_rec) {
   int64_t n_wg = 0;
   phaseA_chunks(HASHED, from_rec, a.n_items, a.tile_items, &n_wg);
   a.tiles_per_wg = from_rec ? AKeys<HASHED, true>::kTilesPerWg : AKeys<HASHED, false>::kTilesPerWg;
-  static int dbg = [] {
-    const char* e = getenv("DQ_FREQ_DEBUG");
-    return e ? atoi(e) : 0;
-  }();
   unsigned long long* clk = nullptr;
-  if (dbg >= 2 && hipMalloc(&clk, 16 * 8 * sizeof(unsigned long long)) == hipSuccess)
+  if (freq_debug_level() >= 2 && hipMalloc(&clk, 16 * 8 * sizeof(unsigned long long)) == hipSuccess)
     (void)hipMemset(clk, 0, 16 * 8 * sizeof(unsigned long long));
   else
     clk = nullptr;
@@ -4810,8 +4370,6 @@ static dq_status launch_phaseA_small(dq_freq* f, AArgs& a) {
   HIP_TRY(hipGetLastError());
   return DQ_OK;
 }
-
-static const uint8_t* arena_of(const dq_freq* f) { return f->arena_view ? f->arena_view : f->arena.p; }
 
 static AArgs base_args(dq_freq* f) {
   AArgs a;
@@ -5037,7 +4595,7 @@ static dq_status finalize_b(dq_freq* f) {
   f->R = R;
   f->s_bits = s;
   f->n_units = u;
-  if (getenv("DQ_FREQ_DEBUG")) {
+  if (freq_debug().set) {
     fprintf(stderr, "dq_freq phase A: notready=%llu diff=%llu full=%llu bypass_tiles=%llu\n",
             (unsigned long long)f->h_counters[C_DBG_NOTREADY],
             (unsigned long long)f->h_counters[C_DBG_DIFF], (unsigned long long)f->h_counters[C_DBG_FULL],
@@ -5190,7 +4748,33 @@ static bool pk_ok(const dq_freq* f) {
   return f->s_bits >= kMinPkSubBits && f->h_counters[C_MAXCNT] < (1ULL << (f->s_bits - 3));
 }
 
-static dq_status finalize_c(dq_freq* f, bool want_groups, bool want_cand) {
+// The one place that chooses a phase-C instantiation.  first: a first pass over whole partitions
+// (a hashed table's recounts run freq_phaseC); pk: packed slots (exact first passes, pk_ok); big:
+// one 1024-thread workgroup per CU, on grid_pk workgroups; a.dbg_clock: the stamping ones.
+static void launch_phase_c(const dq_freq* f, const CArgs& a, bool first, bool pk, bool big,
+                           unsigned grid, unsigned grid_pk) {
+  const bool clk = a.dbg_clock != nullptr;
+  if (f->exact && clk && pk && big)
+    hipLaunchKernelGGL((freq_phaseC_x<true, true, true>), dim3(grid_pk), dim3(kCThreadsX<true>), 0, f->stream, a);
+  else if (f->exact && clk && pk)
+    hipLaunchKernelGGL((freq_phaseC_x<true, true>), dim3(grid), dim3(kCThreads), 0, f->stream, a);
+  else if (f->exact && clk)
+    hipLaunchKernelGGL((freq_phaseC_x<true, false>), dim3(grid), dim3(kCThreads), 0, f->stream, a);
+  else if (f->exact && pk && big)
+    hipLaunchKernelGGL((freq_phaseC_x<false, true, true>), dim3(grid_pk), dim3(kCThreadsX<true>), 0, f->stream, a);
+  else if (f->exact && pk)
+    hipLaunchKernelGGL((freq_phaseC_x<false, true>), dim3(grid), dim3(kCThreads), 0, f->stream, a);
+  else if (f->exact)
+    hipLaunchKernelGGL((freq_phaseC_x<false, false>), dim3(grid), dim3(kCThreads), 0, f->stream, a);
+  else if (first && clk)
+    hipLaunchKernelGGL(freq_phaseC_h<true>, dim3(grid), dim3(kCThreads), 0, f->stream, a);
+  else if (first)
+    hipLaunchKernelGGL(freq_phaseC_h<false>, dim3(grid), dim3(kCThreads), 0, f->stream, a);
+  else
+    hipLaunchKernelGGL(freq_phaseC<true>, dim3(grid), dim3(kCThreads), 0, f->stream, a);
+}
+
+dq_status dq::finalize_c(dq_freq* f, bool want_groups, bool want_cand) {
   bool reduced = false;  // f->red already holds this pass's sums
   bool read_back = false;  // red_h / cw_h hold the reduction and the counters (one wait for both)
   unsigned long long red_h[6], cw_h[C_N + 1];
@@ -5251,12 +4835,8 @@ static dq_status finalize_c(dq_freq* f, bool want_groups, bool want_cand) {
     a.ovf_out = f->ovf_a.p;
     a.ovf_n = f->ovf_n.p;
     a.n_work = (int32_t)P;
-    static int dbg = [] {
-      const char* e = getenv("DQ_FREQ_DEBUG");
-      return e ? atoi(e) : 0;
-    }();
     unsigned long long* clk = nullptr;
-    if (dbg >= 2 && hipMalloc(&clk, 16 * 8 * sizeof(unsigned long long)) == hipSuccess)
+    if (freq_debug_level() >= 2 && hipMalloc(&clk, 16 * 8 * sizeof(unsigned long long)) == hipSuccess)
       (void)hipMemset(clk, 0, 16 * 8 * sizeof(unsigned long long));
     else
       clk = nullptr;
@@ -5271,24 +4851,7 @@ static dq_status finalize_c(dq_freq* f, bool want_groups, bool want_cand) {
       // (packed, partitions of > 2048 records on average: one 1024-thread workgroup per CU)
       const bool big = pk && f->R > (uint64_t)P * 2048;
       const unsigned grid_pk = (unsigned)std::min<int64_t>(P, std::max(1, cus));
-      if (f->exact && clk && pk && big)
-        hipLaunchKernelGGL((freq_phaseC_x<true, true, true>), dim3(grid_pk), dim3(kCThreadsX<true>), 0, f->stream, a);
-      else if (f->exact && clk && pk)
-        hipLaunchKernelGGL((freq_phaseC_x<true, true>), dim3(grid), dim3(kCThreads), 0, f->stream, a);
-      else if (f->exact && clk)
-        hipLaunchKernelGGL((freq_phaseC_x<true, false>), dim3(grid), dim3(kCThreads), 0, f->stream, a);
-      else if (f->exact && pk && big)
-        hipLaunchKernelGGL((freq_phaseC_x<false, true, true>), dim3(grid_pk), dim3(kCThreadsX<true>), 0, f->stream, a);
-      else if (f->exact && pk)
-        hipLaunchKernelGGL((freq_phaseC_x<false, true>), dim3(grid), dim3(kCThreads), 0, f->stream, a);
-      else if (f->exact)
-        hipLaunchKernelGGL((freq_phaseC_x<false, false>), dim3(grid), dim3(kCThreads), 0, f->stream, a);
-      else if (round == 0 && clk)
-        hipLaunchKernelGGL(freq_phaseC_h<true>, dim3(grid), dim3(kCThreads), 0, f->stream, a);
-      else if (round == 0)
-        hipLaunchKernelGGL(freq_phaseC_h<false>, dim3(grid), dim3(kCThreads), 0, f->stream, a);
-      else
-        hipLaunchKernelGGL(freq_phaseC<true>, dim3(grid), dim3(kCThreads), 0, f->stream, a);
+      launch_phase_c(f, a, round == 0, pk, big, grid, grid_pk);
       HIP_TRY(hipGetLastError());
       if (round == 0) {  // the reduction, queued before the wait: read with ovf_n if none overflow
         dq_status rs = launch_reduce(f, P);
@@ -5392,7 +4955,7 @@ static dq_status finalize_c(dq_freq* f, bool want_groups, bool want_cand) {
 }
 
 // The materialised groups, compacted: f->compact[0 .. f->n_compact).
-static dq_status compact_groups(dq_freq* f) {
+dq_status dq::compact_groups(dq_freq* f) {
   dq_status st = finalize_c(f, true, false);
   if (st != DQ_OK) return st;
   if (f->n_compact >= 0) return DQ_OK;
@@ -5417,538 +4980,6 @@ static dq_status compact_groups(dq_freq* f) {
   }
   f->n_compact = (int64_t)tot;
   return DQ_OK;
-}
-
-// str_row_hash of an arena-encoded utf8 part (tag, length, bytes zero-padded to 4): the bytes
-// start dword-aligned, so a key of <= 16 bytes is read as its dwords (no byte loop), masked to its
-// length, and hashed from registers (str_row_hash_reg == str_row_hash for such keys).
-DQ_DEV uint64_t enc_str_hash(const uint32_t* part) {
-  const int32_t len = (int32_t)part[1];
-  if (len > 16) return str_row_hash(SView{reinterpret_cast<const uint8_t*>(part + 2), len});
-  const int nd = (len + 3) >> 2;
-  uint32_t d[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) d[k] = k < nd ? part[2 + k] : 0u;
-  const uint32_t tail = (uint32_t)len & 3u;
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    if (tail && k == nd - 1) d[k] &= (1u << (8 * tail)) - 1u;
-  const uint64_t w0 = (uint64_t)d[0] | ((uint64_t)d[1] << 32);
-  const uint64_t w1 = (uint64_t)d[2] | ((uint64_t)d[3] << 32);
-  return str_row_hash_reg(w0, w1, len);
-}
-
-// The marginal of key column k over a hashed table's groups, as records for a one-key table:
-// column k's part of a group's encoded key IS the one-column encoding of that value, so a
-// record points into the same arena (enc_off), and carries the group's count.  Exact output
-// (fixed-width column): key = the value.  Hashed output (utf8): key = the one-column row hash.
-__global__ void freq_project(const Group* __restrict__ g, int64_t n, const uint8_t* __restrict__ arena,
-                             PartTypes t, int k, RecIn* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t* enc = reinterpret_cast<const uint32_t*>(arena + g[i].rep);
-  uint32_t w = 0;
-  for (int c = 0; c < k; ++c) {  // skip the columns before k
-    const uint32_t tag = enc[w++];
-    if (!tag) continue;
-    if (t.types[c] == DQ_UTF8) w += 1 + pad4(enc[w]) / 4;
-    else w += 2;
-  }
-  RecIn r;
-  r.count = g[i].count;
-  r.enc_off = g[i].rep + 4ull * w;
-  if (t.types[k] == DQ_UTF8) {
-    r.key = enc_str_hash(enc + w);
-  } else {
-    r.key = (uint64_t)enc[w + 1] | ((uint64_t)enc[w + 2] << 32);
-  }
-  out[i] = r;
-}
-
-// Both marginals' records of a two-key table's groups in one pass over the groups and the arena
-// (freq_project for key 0 and key 1).
-__global__ void freq_project2(const Group* __restrict__ g, int64_t n, const uint8_t* __restrict__ arena,
-                              PartTypes t, RecIn* __restrict__ out0, RecIn* __restrict__ out1) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const Group gi = g[i];
-  const uint32_t* enc = reinterpret_cast<const uint32_t*>(arena + gi.rep);
-  uint32_t w = 0;
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    RecIn r;
-    r.count = gi.count;
-    r.enc_off = gi.rep + 4ull * w;
-    const uint32_t tag = enc[w];
-    if (t.types[k] == DQ_UTF8) {
-      r.key = enc_str_hash(enc + w);
-      w += tag ? 2 + pad4(enc[w + 1]) / 4 : 1;
-    } else {
-      r.key = (uint64_t)enc[w + 1] | ((uint64_t)enc[w + 2] << 32);
-      w += tag ? 3 : 1;
-    }
-    RecIn* o = k ? out1 : out0;  // (nullptr: that side's marginal is built another way)
-    if (o) o[i] = r;
-  }
-}
-
-// ---- small marginals (MutualInformation over a low-cardinality column) ----------------------------
-// One pass over the joint groups aggregates each side's marginal in registers and LDS when the
-// side has at most kSmallMarg distinct values per wave and keys of at most 8 encoded words: a wave
-// keeps its values (row hash + encoded words), matches every group's part against them (hash and
-// words), and sums the joint counts per value with one wave reduction per value.  The host merges
-// the waves' lists by (hash, words).  A side with more values, a longer key or two values on one
-// hash is marked failed and takes the general path (a one-key table of the projected records).
-// Also writes every group's row hash of each side (hk[k][i], the hash its marginal is indexed by).
-constexpr int kSmallMarg = 16;
-struct SmallEntry {
-  unsigned long long h, count;
-  uint32_t w[8];
-};
-// freq_small_marginal's per-wave lists of the small sides merged on the device (one workgroup per
-// side): values claimed by hash in an LDS table, counts added, then every entry's words checked
-// against the first entry of its hash -- the host reads a few KB instead of every wave's list (12.6
-// MB for a 1.2e8-group joint, ~4 ms of copies and map inserts).  out_n[k]: the merged values, or
-// kSmallMergeHost (more values than the table takes: the host merges the lists as before), or
-// kSmallMergeClash (two values on one hash, or the side failed: not small).
-constexpr int kSmallMergeSlots = 1024, kSmallMerged = 512;
-constexpr uint32_t kSmallMergeHost = 0xFFFFFFFFu, kSmallMergeClash = 0xFFFFFFFEu;
-__global__ void __launch_bounds__(1024) freq_small_merge(const SmallEntry* __restrict__ ent,
-                                                         const uint32_t* __restrict__ nout, int64_t nw,
-                                                         const unsigned int* __restrict__ fail,
-                                                         SmallEntry* __restrict__ out, uint32_t* __restrict__ out_n) {
-  constexpr int S = kSmallMergeSlots;
-  constexpr unsigned long long kFree = ~0ULL;
-  __shared__ unsigned long long s_h[S], s_c[S], s_first[S];
-  __shared__ uint32_t s_w[S][8];
-  __shared__ uint32_t s_full, s_clash;
-  const int k = blockIdx.x, tid = threadIdx.x;
-  if (fail[k]) {
-    if (tid == 0) out_n[k] = kSmallMergeClash;
-    return;
-  }
-  for (int i = tid; i < S; i += blockDim.x) {
-    s_h[i] = kFree;
-    s_c[i] = 0;
-    s_first[i] = kFree;
-  }
-  if (tid == 0) s_full = s_clash = 0;
-  __syncthreads();
-  // the slot of entry x's hash (claimed when `claim`), or S: none / the table is full
-  auto slot_of = [&](const SmallEntry& e, bool claim) -> uint32_t {
-    uint32_t sl = (uint32_t)e.h & (S - 1);
-    for (int pr = 0; pr < S; ++pr, sl = (sl + 1) & (S - 1)) {
-      const unsigned long long old = claim ? atomicCAS(&s_h[sl], kFree, e.h) : s_h[sl];
-      if (old == e.h || (claim && old == kFree)) return sl;
-      if (!claim && old == kFree) return S;
-    }
-    return S;
-  };
-  // a thread per wave list (its count read once); f(e, x) for each entry x of side k
-  auto for_entries = [&](auto&& f) {
-    for (int64_t gwv = tid; gwv < nw; gwv += blockDim.x) {
-      const uint32_t nl = nout[gwv * 2 + k];
-      for (uint32_t c = 0; c < nl; ++c) f(ent[(gwv * 2 + k) * kSmallMarg + c], gwv * kSmallMarg + c);
-    }
-  };
-  for_entries([&](const SmallEntry& e, int64_t x) {  // claims, counts, the first entry per value
-    const uint32_t sl = e.h == kFree ? (uint32_t)S : slot_of(e, true);
-    if (sl == (uint32_t)S) {
-      s_full = 1;
-      return;
-    }
-    atomicAdd(&s_c[sl], e.count);
-    atomicMin(&s_first[sl], (unsigned long long)x);
-  });
-  __syncthreads();
-  if (s_full) {
-    if (tid == 0) out_n[k] = kSmallMergeHost;
-    return;
-  }
-  for_entries([&](const SmallEntry& e, int64_t x) {  // the first entry of each value: its words
-    const uint32_t sl = slot_of(e, false);
-    if (sl < (uint32_t)S && s_first[sl] == (unsigned long long)x)
-      for (int q = 0; q < 8; ++q) s_w[sl][q] = e.w[q];
-  });
-  __syncthreads();
-  for_entries([&](const SmallEntry& e, int64_t) {  // every entry's words against its value's
-    const uint32_t sl = slot_of(e, false);
-    bool eq = sl < (uint32_t)S;
-    for (int q = 0; q < 8 && eq; ++q) eq = s_w[sl][q] == e.w[q];
-    if (!eq) s_clash = 1;
-  });
-  __syncthreads();
-  if (tid == 0) {
-    uint32_t m = 0;
-    for (int sl = 0; sl < S && m <= (uint32_t)kSmallMerged; ++sl) {
-      if (s_h[sl] == kFree) continue;
-      if (m < (uint32_t)kSmallMerged) {
-        SmallEntry o;
-        o.h = s_h[sl];
-        o.count = s_c[sl];
-        for (int j = 0; j < 8; ++j) o.w[j] = s_w[sl][j];
-        out[(int64_t)k * kSmallMerged + m] = o;
-      }
-      ++m;
-    }
-    out_n[k] = s_clash ? kSmallMergeClash : (m > (uint32_t)kSmallMerged ? kSmallMergeHost : m);
-  }
-}
-
-// A side's part of an encoded key from the 16 words loaded at the key's start: its word count,
-// its row hash (utf8 <= 16 bytes and fixed-width from the words; longer utf8 from memory) and
-// its first 8 words (a side with a longer key is not aggregated here)
-DQ_DEV void small_part(const uint32_t (&e)[16], uint32_t w, bool utf8, const uint32_t* enc, uint32_t& nw,
-                       uint64_t& h, uint32_t (&pw)[8]) {
-  uint32_t ww[10];
-#pragma unroll
-  for (int j = 0; j < 10; ++j) {  // e[w + j] (w <= 6 for a first side of <= 8 words... else memory)
-    uint32_t v = 0;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) v = (uint32_t)q == w + (uint32_t)j ? e[q] : v;
-    ww[j] = w + (uint32_t)j < 16u ? v : enc[w + j];
-  }
-  const uint32_t tag = ww[0];
-  if (utf8) {
-    const uint32_t len = ww[1];
-    nw = tag ? 2u + pad4(len) / 4 : 1u;
-    if (!tag) {
-      h = 0;
-    } else if (len <= 16) {
-      const int nd = (int)((len + 3) >> 2);
-      uint32_t d[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) d[k] = k < nd ? ww[2 + k] : 0u;
-      const uint32_t tail = len & 3u;
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (tail && k == nd - 1) d[k] &= (1u << (8 * tail)) - 1u;
-      h = str_row_hash_reg((uint64_t)d[0] | ((uint64_t)d[1] << 32), (uint64_t)d[2] | ((uint64_t)d[3] << 32),
-                           (int32_t)len);
-    } else {
-      h = enc_str_hash(enc + w);
-    }
-  } else {
-    nw = tag ? 3u : 1u;
-    h = tag ? fmix_bij((uint64_t)ww[1] | ((uint64_t)ww[2] << 32)) : 0;
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) pw[j] = (uint32_t)j < nw ? ww[j] : 0u;
-}
-
-__global__ void __launch_bounds__(256)
-freq_small_marginal(const Group* __restrict__ g, int64_t n, const uint8_t* __restrict__ arena, PartTypes t,
-                    uint32_t try_sides, unsigned long long* __restrict__ hk0, unsigned long long* __restrict__ hk1,
-                    SmallEntry* __restrict__ out, uint32_t* __restrict__ nout, unsigned int* __restrict__ fail,
-                    RecIn* __restrict__ rec0, RecIn* __restrict__ rec1) {
-  __shared__ unsigned long long s_h[4][2][kSmallMarg], s_c[4][2][kSmallMarg];
-  __shared__ uint32_t s_w[4][2][kSmallMarg][8];
-  constexpr int U = 2;  // groups per lane per step, every load of the step in flight together
-  const int lane = (int)__lane_id(), wave = threadIdx.x >> 6;
-  const int64_t gw = (int64_t)blockIdx.x * 4 + wave;
-  int nc[2] = {0, 0};
-  bool dead[2] = {!(try_sides & 1u), !(try_sides & 2u)};
-  for (int64_t base = gw * 64 * U; base < n; base += (int64_t)gridDim.x * 256 * U) {
-    Group gi[U];
-    bool on[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int64_t i = base + u * 64 + lane;
-      on[u] = i < n;
-      gi[u] = g[on[u] ? i : n - 1];
-    }
-    uint32_t e[U][16];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const uint32_t* enc = reinterpret_cast<const uint32_t*>(arena + gi[u].rep);
-#pragma unroll
-      for (int q = 0; q < 16; ++q) e[u][q] = enc[q];
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int64_t i = base + u * 64 + lane;
-      const uint32_t* enc = reinterpret_cast<const uint32_t*>(arena + gi[u].rep);
-      uint32_t w = 0;
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        uint32_t nw, pw[8];
-        uint64_t h;
-        small_part(e[u], w, t.types[k] == DQ_UTF8, enc, nw, h, pw);
-        if (on[u]) (k ? hk1 : hk0)[i] = h;
-        RecIn* ro = k ? rec1 : rec0;  // freq_project2's record of this side, for a general marginal
-        if (ro && on[u]) {            // (a utf8 part's key hash is its row hash)
-          RecIn r;
-          r.key = t.types[k] == DQ_UTF8 ? h : ((uint64_t)pw[1] | ((uint64_t)pw[2] << 32));
-          r.count = gi[u].count;
-          r.enc_off = gi[u].rep + 4ull * w;
-          ro[i] = r;
-        }
-        if (!dead[k] && __ballot(on[u] && (!pw[0] || nw > 8u))) dead[k] = true;  // NULL part, long key
-        if (!dead[k]) {
-          int m = -1;
-          for (int c = 0; c < nc[k]; ++c) {
-            bool eq = on[u] && m < 0 && s_h[wave][k][c] == h;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) eq = eq && s_w[wave][k][c][j] == pw[j];
-            if (eq) m = c;
-          }
-          while (true) {
-            const uint64_t need = __ballot(on[u] && m < 0);
-            if (!need) break;
-            if (nc[k] == kSmallMarg) {
-              dead[k] = true;
-              break;
-            }
-            const int leader = __builtin_ctzll(need);
-            const uint64_t lh = ((uint64_t)__builtin_amdgcn_readlane((int)(h >> 32), leader) << 32) |
-                                (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)h, leader);
-            uint32_t lw[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) lw[j] = (uint32_t)__builtin_amdgcn_readlane((int)pw[j], leader);
-            bool clash = false;  // another value on this hash: not decidable by hash
-            for (int c = 0; c < nc[k]; ++c) clash = clash || s_h[wave][k][c] == lh;
-            if (clash) {
-              dead[k] = true;
-              break;
-            }
-            const int c = nc[k]++;
-            if (lane == 0) {
-              s_h[wave][k][c] = lh;
-              s_c[wave][k][c] = 0;
-#pragma unroll
-              for (int j = 0; j < 8; ++j) s_w[wave][k][c][j] = lw[j];
-            }
-            bool eq = on[u] && m < 0 && h == lh;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) eq = eq && pw[j] == lw[j];
-            if (eq) m = c;
-          }
-          if (!dead[k]) {
-            for (int c = 0; c < nc[k]; ++c) {
-              const uint64_t sum = __ockl_wfred_add_u64(m == c ? gi[u].count : 0ULL);
-              if (lane == 0) s_c[wave][k][c] += sum;
-            }
-          }
-        }
-        w += nw;
-      }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int64_t slot = gw * 2 + k;
-    if (dead[k]) {
-      if (lane == 0) {
-        nout[slot] = 0u;
-        if (try_sides & (1u << k)) atomicOr(&fail[k], 1u);
-      }
-      continue;
-    }
-    if (lane < nc[k]) {
-      SmallEntry en;
-      en.h = s_h[wave][k][lane];
-      en.count = s_c[wave][k][lane];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) en.w[j] = s_w[wave][k][lane][j];
-      out[slot * kSmallMarg + lane] = en;
-    }
-    if (lane == 0) nout[slot] = (uint32_t)nc[k];
-  }
-}
-
-// ---- MutualInformation (MutualInformation.scala:41-84) -----------------------------------------
-// Column k's part of an encoded multi-key group key.
-DQ_DEV const uint32_t* enc_part(const uint32_t* enc, const PartTypes& t, int k) {
-  uint32_t w = 0;
-  for (int c = 0; c < k; ++c) {
-    const uint32_t tag = enc[w++];
-    if (!tag) continue;
-    if (t.types[c] == DQ_UTF8) w += 1 + pad4(enc[w]) / 4;
-    else w += 2;
-  }
-  return enc + w;
-}
-
-// Open-addressing index over a one-key table's groups: slot -> group index + 1 (0 = empty).
-struct Lookup {
-  const Group* g;
-  const uint32_t* slots;
-  uint64_t mask;
-  const uint8_t* arena;
-  int32_t type;
-  int32_t exact;
-  // a marginal group's rep = rep_base + the joint-arena offset of the key part it was made
-  // from (dq_freq_marginal copies the joint arena): a part at that offset IS the group's key
-  uint64_t rep_base;
-};
-
-__global__ void freq_lookup_build(const Group* __restrict__ g, int64_t n, uint64_t mask,
-                                  uint32_t* __restrict__ slots) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  uint64_t s = g[i].h & mask;
-  while (atomicCAS(&slots[s], 0u, (uint32_t)(i + 1)) != 0u) s = (s + 1) & mask;
-}
-
-// The count of the marginal group whose key is the one-column encoding `part`, at offset
-// part_off of the joint arena.
-DQ_DEV uint64_t lookup_count(const Lookup& L, const uint32_t* part, uint64_t part_off) {
-  uint64_t h;
-  if (L.exact) {
-    h = fmix_bij((uint64_t)part[1] | ((uint64_t)part[2] << 32));
-  } else {
-    h = enc_str_hash(part);
-  }
-  for (uint64_t s = h & L.mask;; s = (s + 1) & L.mask) {
-    const uint32_t idx = L.slots[s];
-    if (!idx) return 0;  // not reachable: every joint value has its marginal group
-    const Group& m = L.g[idx - 1];
-    if (m.h != h) continue;
-    if (L.exact || m.rep == L.rep_base + part_off) return m.count;  // (its own record: no compare)
-    const int32_t ty = DQ_UTF8;
-    if (enc_equal_arena(reinterpret_cast<const uint32_t*>(L.arena + m.rep), part, &ty, 1)) return m.count;
-  }
-}
-
-// terms[i] = (pxy/n) ln((pxy/n) / ((px/n)(py/n))), the reference's UDF (MutualInformation.scala:
-// 61-64) with its operation order, per joint group
-__global__ void freq_mi_terms(const Group* __restrict__ gj, int64_t n, const uint8_t* __restrict__ arena,
-                              PartTypes t, Lookup X, Lookup Y, double total, double* __restrict__ terms) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t* enc = reinterpret_cast<const uint32_t*>(arena + gj[i].rep);
-  const uint32_t* ex = enc_part(enc, t, 0);
-  const uint32_t* ey = enc_part(enc, t, 1);
-  const double px = (double)lookup_count(X, ex, gj[i].rep + 4ull * (uint64_t)(ex - enc));
-  const double py = (double)lookup_count(Y, ey, gj[i].rep + 4ull * (uint64_t)(ey - enc));
-  const double pxy = (double)gj[i].count;
-  terms[i] = (pxy / total) * log((pxy / total) / ((px / total) * (py / total)));
-}
-
-// A marginal's groups by row hash, for a table with no two keys on one 64-bit hash (its phase C
-// counted no collision): slot = {row hash, count}, count 0 = empty, so a lookup is one probe
-// sequence with no key bytes compared.
-struct CountSlot {
-  unsigned long long h, count;
-};
-// -sum (c/n) ln(c/n) over a small marginal's value counts (count 0: an empty slot), as the
-// fixed-point sum phase C keeps (same device entropy_term, so the same bits as a table's)
-__global__ void __launch_bounds__(256) freq_slots_entropy(const CountSlot* __restrict__ t, uint64_t n_slots,
-                                                          double num_rows, unsigned long long* out) {
-  fix128 e = 0;
-  for (uint64_t i = threadIdx.x; i < n_slots; i += 256)
-    if (t[i].count) e += fix_of(entropy_term(t[i].count, num_rows));
-  e = wave_sum_fix(e);
-  if (__lane_id() == 0 && e) atomic_add_fix(out, e);
-}
-__global__ void freq_count_index(const Group* __restrict__ g, int64_t n, uint64_t mask,
-                                 CountSlot* __restrict__ slots) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const Group gi = g[i];
-  uint64_t s = gi.h & mask;
-  while (atomicCAS(&slots[s].count, 0ULL, (unsigned long long)gi.count) != 0ULL) s = (s + 1) & mask;
-  slots[s].h = gi.h;
-}
-// Per-partition form (the marginal's phase C partitions, built in LDS, no global atomics):
-// partition p = h >> part_shift owns slots [pbase[p], pbase[p] + 2^plog[p]), probed from h's low
-// bits.  pbase == nullptr: one table of mask + 1 slots.
-struct CountIndex {
-  const CountSlot* slots;
-  uint64_t mask;
-  const unsigned long long* pbase;
-  const uint8_t* plog;
-  int part_shift;
-};
-constexpr int kIdxMaxLog = 12;  // the largest per-partition table built in LDS (64 KB)
-__global__ void __launch_bounds__(256)
-freq_count_index_parts(const Group* __restrict__ groups, const unsigned long long* __restrict__ part_off,
-                       const unsigned long long* __restrict__ part_groups, int64_t P,
-                       const unsigned long long* __restrict__ pbase, const uint8_t* __restrict__ plog,
-                       CountSlot* __restrict__ slots) {
-  __shared__ unsigned long long s_h[1 << kIdxMaxLog], s_c[1 << kIdxMaxLog];
-  for (int64_t p = blockIdx.x; p < P; p += gridDim.x) {
-    const uint32_t R = 1u << plog[p];
-    const uint64_t off = part_off[p], n = part_groups[p];
-    for (uint32_t j = threadIdx.x; j < R; j += 256) s_c[j] = 0;
-    __syncthreads();
-    for (uint64_t i = threadIdx.x; i < n; i += 256) {
-      const Group gi = groups[off + i];
-      uint32_t sl = (uint32_t)gi.h & (R - 1);
-      while (atomicCAS(&s_c[sl], 0ULL, (unsigned long long)gi.count) != 0ULL) sl = (sl + 1) & (R - 1);
-      s_h[sl] = gi.h;
-    }
-    __syncthreads();
-    CountSlot* out = slots + pbase[p];
-    for (uint32_t j = threadIdx.x; j < R; j += 256) out[j] = CountSlot{s_c[j] ? s_h[j] : 0ULL, s_c[j]};
-    __syncthreads();
-  }
-}
-DQ_DEV uint64_t count_of(const CountIndex& x, uint64_t h) {
-  const CountSlot* sl = x.slots;
-  uint64_t mask = x.mask;
-  if (x.pbase) {
-    const uint64_t p = h >> x.part_shift;
-    sl += x.pbase[p];
-    mask = (1ULL << x.plog[p]) - 1;
-  }
-  for (uint64_t s = h & mask;; s = (s + 1) & mask) {
-    const CountSlot c = sl[s];
-    if (c.h == h || c.count == 0) return c.count;  // (count 0: not reachable, every joint value has its group)
-  }
-}
-// freq_mi_terms with both marginals looked up by the row hashes the projection computed (exact
-// keys: the bijective hash of the value), same arithmetic and order
-// (k0 / k1: each side's key of group i at k[i * stride]: a RecIn's key (stride 3; exact: the
-// value, hashed here) or freq_small_marginal's row hash (stride 1))
-__global__ void freq_mi_terms_h(const Group* __restrict__ gj, int64_t n, const uint64_t* __restrict__ k0,
-                                int st0, const uint64_t* __restrict__ k1, int st1, int exact0, int exact1,
-                                CountIndex x0, CountIndex x1, double total, double* __restrict__ terms) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint64_t h0 = exact0 ? fmix_bij(k0[i * st0]) : k0[i * st0];
-  const uint64_t h1 = exact1 ? fmix_bij(k1[i * st1]) : k1[i * st1];
-  const double px = (double)count_of(x0, h0);
-  const double py = (double)count_of(x1, h1);
-  const double pxy = (double)gj[i].count;
-  terms[i] = (pxy / total) * log((pxy / total) / ((px / total) * (py / total)));
-}
-
-// Order-independent sum of the MutualInformation terms (the joint groups' order is phase C's
-// output order, which varies from run to run): each term in fixed point (fix_of), summed as
-// integers; a non-finite term (a marginal count that is not there) is added as a double beside
-// (NaN / inf sums do not depend on order either).  partial[b] = {lo, hi, non-finite sum bits}.
-__global__ void __launch_bounds__(256) freq_sum_fix(const double* __restrict__ x, int64_t n,
-                                                    unsigned long long* __restrict__ partial) {
-  __shared__ fix128 s_red[256 / 64];
-  __shared__ double s_nf[256 / 64];
-  fix128 acc = 0;
-  double nf = 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const double t = x[i];
-    if (fabs(t) < 16384.0) acc += fix_of(t);
-    else nf += t;  // (NaN fails the test too)
-  }
-  acc = wave_sum_fix(acc);
-  nf = block_sum_f64(nf, s_nf);
-  if (__lane_id() == 0) s_red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    fix128 t = 0;
-    for (int w = 0; w < 256 / 64; ++w) t += s_red[w];
-    store_fix(partial + 3 * blockIdx.x, t);
-    partial[3 * blockIdx.x + 2] = __builtin_bit_cast(unsigned long long, nf);
-  }
-}
-
-static PartTypes part_types(const dq_freq* f, int parts) {
-  PartTypes t;
-  memset(&t, 0, sizeof(t));
-  for (int k = 0; k < f->n_keys; ++k) t.types[k] = f->types[k];
-  t.n_keys = f->n_keys;
-  t.exact = f->exact ? 1 : 0;
-  t.parts = (uint32_t)parts;
-  return t;
 }
 
 // Records (+ var bytes) of `n` device groups cut into `parts` owner segments.
@@ -6133,20 +5164,6 @@ static int freq_phys_type(int t) {
   if (DQ_TYPE_ID(t) == DQ_DECIMAL128) return DQ_DECIMAL_PRECISION(t) <= 18 ? DQ_INT64 : DQ_UTF8;
   return t;
 }
-
-namespace dq {
-__global__ void dec_narrow_kernel(const uint64_t* __restrict__ in, int64_t* __restrict__ out,
-                                  int64_t rows) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < rows;
-       i += (int64_t)gridDim.x * blockDim.x)
-    out[i] = (int64_t)in[2 * i];
-}
-__global__ void iota16_kernel(int32_t* __restrict__ out, int64_t n) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x)
-    out[i] = (int32_t)(16 * i);
-}
-}  // namespace dq
 
 static dq_status physical_keys(dq_freq* f, const dq_column* keys, int n_keys, hipStream_t st,
                                dq_column* out) {
@@ -6472,403 +5489,6 @@ extern "C" dq_status dq_freq_summarize_keys(dq_freq* f, dq_freq_summary* out) {
   return DQ_OK;
 }
 
-static dq_status marginal_of(dq_freq* joint, int key_index, dq_freq* out, void* hip_stream,
-                             bool borrow);
-static dq_status add_records(dq_freq* f, const dq_freq_record* records, const uint8_t* var,
-                             int n_src, const int64_t* src_records, const int64_t* src_var_bytes,
-                             int64_t num_rows, const int64_t* special, int null_as_group,
-                             void* hip_stream, bool borrow);
-
-extern "C" dq_status dq_freq_marginal(dq_freq* joint, int key_index, dq_freq* out,
-                                     void* hip_stream) {
-  return marginal_of(joint, key_index, out, hip_stream, false);
-}
-
-// borrow: the marginal reads the joint table's arena in place (it must die first)
-static dq_status marginal_of(dq_freq* joint, int key_index, dq_freq* out, void* hip_stream,
-                             bool borrow) {
-  if (!joint || !out) return fail(DQ_ERR_INVALID_ARGUMENT, "null argument");
-  if (joint->exact || joint->n_keys < 2) return fail(DQ_ERR_INVALID_ARGUMENT, "not a multi-key table");
-  if (key_index < 0 || key_index >= joint->n_keys) return fail(DQ_ERR_INVALID_ARGUMENT, "bad key index");
-  if (out->n_keys != 1 || out->logical[0] != joint->logical[key_index])
-    return fail(DQ_ERR_WRONG_TYPE, "the marginal table must have one key of the column's type");
-  if (joint->mode_null_as_group > 0) return fail(DQ_ERR_UNSUPPORTED, "marginal of a Histogram table");
-  HIP_TRY(hipSetDevice(joint->device));
-  dq_status st = compact_groups(joint);
-  if (st != DQ_OK) return st;
-  const int64_t n = joint->n_compact;
-  DevBuf<RecIn> rec;
-  HIP_TRY(rec.ensure(std::max<int64_t>(n, 1)));
-  if (n) {
-    hipLaunchKernelGGL(freq_project, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, joint->stream,
-                       joint->compact.p, n, arena_of(joint), part_types(joint, 1), key_index, rec.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(joint->stream));
-  }
-  static const int dbg = [] {
-    const char* e = getenv("DQ_FREQ_DEBUG");
-    return e ? atoi(e) : 0;
-  }();
-  const auto t0 = std::chrono::steady_clock::now();
-  const int64_t rc[1] = {n};
-  const int64_t vb[1] = {(int64_t)((joint->arena_used + 7) & ~7ULL)};
-  const int64_t special[3] = {0, 0, (int64_t)joint->h_counters[C_NULL_ROWS]};
-  st = add_records(out, reinterpret_cast<const dq_freq_record*>(rec.p), arena_of(joint), 1, rc, vb,
-                   joint->num_rows, special, 0, hip_stream, borrow && !out->exact);
-  if (st != DQ_OK) return st;
-  HIP_TRY(hipStreamSynchronize(reinterpret_cast<hipStream_t>(hip_stream)));
-  if (dbg)
-    fprintf(stderr, "dq_freq marginal %d: records added in %.2f ms\n", key_index,
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-  return DQ_OK;
-}
-
-extern "C" dq_status dq_freq_mutual_information(dq_freq* joint, double* mi, int* is_null,
-                                               void* hip_stream) {
-  if (!joint || !mi || !is_null) return fail(DQ_ERR_INVALID_ARGUMENT, "null argument");
-  if (joint->exact || joint->n_keys != 2)
-    return fail(DQ_ERR_INVALID_ARGUMENT, "MutualInformation needs a two-key grouping table");
-  HIP_TRY(hipSetDevice(joint->device));
-  dq_status st = compact_groups(joint);
-  if (st != DQ_OK) return st;
-  const int64_t n = joint->n_compact;
-  *mi = 0.0;
-  *is_null = n == 0 ? 1 : 0;  // sum over no joint groups is NULL
-  if (!n) return DQ_OK;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
-  static const int dbg = [] {  // DQ_FREQ_DEBUG: the MI pass's steps, timed (synchronising)
-    const char* e = getenv("DQ_FREQ_DEBUG");
-    return e ? atoi(e) : 0;
-  }();
-  auto t_last = std::chrono::steady_clock::now();
-  auto stamp = [&](const char* what) {
-    if (!dbg) return;
-    (void)hipStreamSynchronize(stream);
-    const auto t = std::chrono::steady_clock::now();
-    fprintf(stderr, "dq_freq MI %s: %.2f ms\n", what,
-            std::chrono::duration<double, std::milli>(t - t_last).count());
-    t_last = t;
-  };
-  dq_freq* marg[2] = {nullptr, nullptr};
-  DevBuf<uint32_t> slots[2];
-  DevBuf<CountSlot> cslots[2];
-  uint64_t cmask[2] = {0, 0};
-  Lookup L[2];
-  dq_status res = DQ_OK;
-  const char* fl = getenv("DQ_FREQ_MI_LOOKUP");  // =1: the byte-compare lookups (A/B, tests)
-  const bool force_lookup = fl && atoi(fl) != 0;
-  const char* fsm = getenv("DQ_FREQ_MI_NOSMALL");  // =1: no small-marginal pass (A/B, tests)
-  bool small[2] = {false, false};  // side k's marginal aggregated by freq_small_marginal
-  DevBuf<unsigned long long> hk[2];
-  // each side's records of the joint groups (kept: the lookups read their keys), written by the
-  // small-marginal pass for both sides (a side that is not small needs them; otherwise
-  // freq_project2 makes them in a pass of its own)
-  DevBuf<RecIn> rec[2];
-  bool rec_done = false;
-  if (!force_lookup && !(fsm && atoi(fsm))) {
-    const unsigned grid = (unsigned)std::min<int64_t>(std::max<int64_t>((n + 511) / 512, 1), 2048);
-    const int64_t nw = (int64_t)grid * 4;
-    DevBuf<SmallEntry> ent;
-    DevBuf<uint32_t> nout;
-    DevBuf<unsigned int> sfail;
-    HIP_TRY(hk[0].ensure(n));
-    HIP_TRY(hk[1].ensure(n));
-    HIP_TRY(ent.ensure((size_t)nw * 2 * kSmallMarg));
-    HIP_TRY(nout.ensure((size_t)nw * 2));
-    HIP_TRY(sfail.ensure(2));
-    HIP_TRY(rec[0].ensure(n));
-    HIP_TRY(rec[1].ensure(n));
-    HIP_TRY(hipMemsetAsync(sfail.p, 0, 8, stream));
-    hipLaunchKernelGGL(freq_small_marginal, dim3(grid), dim3(256), 0, stream, joint->compact.p, n,
-                       arena_of(joint), part_types(joint, 1), 3u, hk[0].p, hk[1].p, ent.p, nout.p, sfail.p,
-                       rec[0].p, rec[1].p);
-    HIP_TRY(hipGetLastError());
-    rec_done = true;
-    unsigned int hf[2];
-    HIP_TRY(d2h(hf, sfail.p, 8, stream));
-    if (!hf[0] || !hf[1]) {  // merge the waves' lists of each small side by (hash, words)
-      DevBuf<SmallEntry> mo;
-      DevBuf<uint32_t> mn;
-      HIP_TRY(mo.ensure(2 * (size_t)kSmallMerged));
-      HIP_TRY(mn.ensure(2));
-      hipLaunchKernelGGL(freq_small_merge, dim3(2), dim3(1024), 0, stream, ent.p, nout.p, nw, sfail.p, mo.p, mn.p);
-      HIP_TRY(hipGetLastError());
-      uint32_t hm[2];
-      HIP_TRY(d2h(hm, mn.p, 8, stream));
-      const char* hmg = getenv("DQ_FREQ_MI_HOSTMERGE");  // =1: the host merge (A/B, tests)
-      if (hmg && atoi(hmg))
-        for (int k = 0; k < 2; ++k)
-          if (hm[k] != kSmallMergeClash) hm[k] = kSmallMergeHost;
-      std::vector<SmallEntry> hme(2 * (size_t)kSmallMerged);
-      HIP_TRY(d2h(hme.data(), mo.p, hme.size() * sizeof(SmallEntry), stream));
-      // (the host merge of every wave's list, for a side the device table could not take)
-      std::vector<uint32_t> hn;
-      std::vector<SmallEntry> he;
-      if ((!hf[0] && hm[0] == kSmallMergeHost) || (!hf[1] && hm[1] == kSmallMergeHost)) {
-        hn.resize((size_t)nw * 2);
-        he.resize((size_t)nw * 2 * kSmallMarg);
-        HIP_TRY(d2h(hn.data(), nout.p, hn.size() * 4, stream));
-        HIP_TRY(d2h(he.data(), ent.p, he.size() * sizeof(SmallEntry), stream));
-      }
-      for (int k = 0; k < 2; ++k) {
-        if (hf[k] || hm[k] == kSmallMergeClash) continue;
-        const bool host = hm[k] == kSmallMergeHost;
-        // (merged on the device: one list of hm[k] entries, as if from one wave)
-        const int64_t lists = host ? nw : 1;
-        std::map<uint64_t, std::pair<std::array<uint32_t, 8>, uint64_t>> vals;
-        bool ok = true;
-        for (int64_t gwv = 0; gwv < lists && ok; ++gwv)
-          for (uint32_t c = 0; c < (host ? hn[gwv * 2 + k] : hm[k]) && ok; ++c) {
-            const SmallEntry& e = host ? he[((size_t)gwv * 2 + k) * kSmallMarg + c]
-                                       : hme[(size_t)k * kSmallMerged + c];
-            std::array<uint32_t, 8> wv;
-            for (int q = 0; q < 8; ++q) wv[q] = e.w[q];
-            auto it = vals.find(e.h);
-            if (it == vals.end()) vals.emplace(e.h, std::make_pair(wv, (uint64_t)e.count));
-            else if (it->second.first != wv) ok = false;  // two values on one hash
-            else it->second.second += e.count;
-          }
-        if (!ok) continue;
-        uint64_t cap = 2;
-        while (cap < 2 * (uint64_t)vals.size()) cap <<= 1;
-        std::vector<CountSlot> tab(cap, CountSlot{0, 0});
-        for (const auto& kv : vals) {
-          uint64_t sl = kv.first & (cap - 1);
-          while (tab[sl].count) sl = (sl + 1) & (cap - 1);
-          tab[sl] = CountSlot{kv.first, kv.second.second};
-        }
-        HIP_TRY(cslots[k].ensure(cap));
-        HIP_TRY(hipMemcpy(cslots[k].p, tab.data(), cap * sizeof(CountSlot), hipMemcpyHostToDevice));
-        cmask[k] = cap - 1;
-        small[k] = true;
-      }
-    }
-    stamp("small marginals");
-  }
-  for (int k = 0; k < 2; ++k)
-    if (!small[k]) HIP_TRY(rec[k].ensure(n));
-  if (!rec_done && (!small[0] || !small[1])) {
-    hipLaunchKernelGGL(freq_project2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, joint->stream,
-                       joint->compact.p, n, arena_of(joint), part_types(joint, 1),
-                       small[0] ? nullptr : rec[0].p, small[1] ? nullptr : rec[1].p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(joint->stream));
-  }
-  stamp("project");
-  bool by_hash = !force_lookup;  // no marginal has two keys on one 64-bit hash
-  for (int k = 0; k < 2 && res == DQ_OK; ++k) {
-    if (small[k]) continue;
-    const int32_t ty = joint->types[k];
-    res = dq_freq_create(joint->device, 1, &ty, 0, &marg[k]);
-    stamp(k ? "marginal 1 create" : "marginal 0 create");
-    if (res == DQ_OK) {
-      const int64_t rc[1] = {n};
-      const int64_t vb[1] = {(int64_t)((joint->arena_used + 7) & ~7ULL)};
-      const int64_t special[3] = {0, 0, (int64_t)joint->h_counters[C_NULL_ROWS]};
-      res = add_records(marg[k], reinterpret_cast<const dq_freq_record*>(rec[k].p), arena_of(joint), 1, rc,
-                        vb, joint->num_rows, special, 0, hip_stream, !marg[k]->exact);
-    }
-    stamp(k ? "marginal 1 records" : "marginal 0 records");
-    // statistics first: the entropy identity below may make the groups unnecessary
-    if (res == DQ_OK) res = finalize_c(marg[k], false, false);
-    stamp(k ? "marginal 1 statistics" : "marginal 0 statistics");
-    if (res != DQ_OK) break;
-    if (marg[k]->h_counters[C_COLLISIONS]) by_hash = false;
-  }
-  // MI = E(X) + E(Y) - E(X, Y), every entropy normalised by the same numRows as the reference's
-  // terms ((pxy/n) ln((pxy/n) / ((px/n)(py/n))) summed over the joint groups, the marginals
-  // summed over them too: MutualInformation.scala:41-75) -- exact algebra over the fixed-point
-  // sums of the tables' own -p ln p terms (the joint's and a general side's from phase C, a small
-  // side's from its value counts with the same device term).  Taken when MI >= 1/100 of
-  // E(X) + E(Y) + E(X, Y): each entropy's rounding is then below 1e-13 of MI (two columns close
-  // to independent keep the per-group terms, whose sum does not cancel).
-  if (res == DQ_OK) {
-    fix128 ex[2];
-    for (int k = 0; k < 2 && res == DQ_OK; ++k) {
-      if (!small[k]) {
-        ex[k] = marg[k]->st_entropy_fix;
-        continue;
-      }
-      DevBuf<unsigned long long> acc;
-      unsigned long long w[2];
-      if (acc.ensure(2) != hipSuccess || hipMemsetAsync(acc.p, 0, 16, stream) != hipSuccess) {
-        res = fail(DQ_ERR_OUT_OF_MEMORY, "MutualInformation entropy");
-        break;
-      }
-      hipLaunchKernelGGL(freq_slots_entropy, dim3(1), dim3(256), 0, stream, cslots[k].p, cmask[k] + 1,
-                         (double)joint->num_rows, acc.p);
-      if (hipGetLastError() != hipSuccess || d2h(w, acc.p, 16, stream) != hipSuccess) {
-        res = fail(DQ_ERR_DEVICE, "MutualInformation entropy");
-        break;
-      }
-      ex[k] = (fix128)(((unsigned __int128)w[1] << 64) | w[0]);
-    }
-    if (res == DQ_OK) {
-      const fix128 exy = joint->st_entropy_fix, v = ex[0] + ex[1] - exy;
-      if (v > 0 && v * 100 >= ex[0] + ex[1] + exy) {
-        *mi = fix_to_f64(v);
-        for (int k = 0; k < 2; ++k)
-          if (marg[k]) dq_freq_destroy(marg[k]);
-        stamp("entropy identity");
-        return DQ_OK;
-      }
-    }
-  }
-  for (int k = 0; k < 2 && res == DQ_OK; ++k) {  // the per-group terms: each general side's groups
-    if (small[k]) continue;
-    // (the groups stay where phase C put them, per partition; compacted only for the
-    // byte-compare lookups)
-    res = finalize_c(marg[k], true, false);
-    stamp(k ? "marginal 1 groups" : "marginal 0 groups");
-  }
-  if (res == DQ_OK && !by_hash && (small[0] || small[1])) {
-    // a general side counted a hash collision: the byte-compare lookups need both sides as
-    // tables, so the small sides are built the general way too
-    for (int k = 0; k < 2 && res == DQ_OK; ++k) {
-      if (!small[k]) continue;
-      small[k] = false;
-      if (rec[k].ensure(n) != hipSuccess) {
-        res = fail(DQ_ERR_OUT_OF_MEMORY, "MutualInformation records");
-        break;
-      }
-      hipLaunchKernelGGL(freq_project, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, joint->stream,
-                         joint->compact.p, n, arena_of(joint), part_types(joint, 1), k, rec[k].p);
-      const int32_t ty = joint->types[k];
-      res = dq_freq_create(joint->device, 1, &ty, 0, &marg[k]);
-      if (res == DQ_OK) {
-        const int64_t rc[1] = {n};
-        const int64_t vb[1] = {(int64_t)((joint->arena_used + 7) & ~7ULL)};
-        const int64_t special[3] = {0, 0, (int64_t)joint->h_counters[C_NULL_ROWS]};
-        res = add_records(marg[k], reinterpret_cast<const dq_freq_record*>(rec[k].p), arena_of(joint), 1,
-                          rc, vb, joint->num_rows, special, 0, hip_stream, !marg[k]->exact);
-      }
-      if (res == DQ_OK) res = compact_groups(marg[k]);
-    }
-  }
-  CountIndex X[2];
-  DevBuf<unsigned long long> pbase[2];
-  DevBuf<uint8_t> plog[2];
-  for (int k = 0; k < 2; ++k) X[k] = CountIndex{cslots[k].p, cmask[k], nullptr, nullptr, 0};
-  for (int k = 0; k < 2 && res == DQ_OK; ++k) {
-    if (small[k]) continue;
-    const int32_t ty = joint->types[k];
-    if (by_hash) {  // per partition, in LDS, when every partition's table fits
-      dq_freq* mg = marg[k];
-      const int64_t P = (int64_t)kBuckets << mg->s_bits;
-      std::vector<unsigned long long> cnt(P), base(P);
-      std::vector<uint8_t> lg(P);
-      if (d2h(cnt.data(), mg->part_groups.p, P * 8, mg->stream) != hipSuccess) {
-        res = fail(DQ_ERR_DEVICE, "marginal index");
-        break;
-      }
-      unsigned long long tot = 0;
-      bool fits = true;
-      for (int64_t q = 0; q < P; ++q) {
-        int l = 4;
-        while ((1ULL << l) < 2 * cnt[q]) ++l;
-        fits = fits && l <= kIdxMaxLog;
-        lg[q] = (uint8_t)l;
-        base[q] = tot;
-        tot += 1ULL << l;
-      }
-      if (fits) {
-        if (cslots[k].ensure(tot) != hipSuccess || pbase[k].ensure(P) != hipSuccess ||
-            plog[k].ensure(P) != hipSuccess ||
-            hipMemcpy(pbase[k].p, base.data(), P * 8, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(plog[k].p, lg.data(), P, hipMemcpyHostToDevice) != hipSuccess) {
-          res = fail(DQ_ERR_OUT_OF_MEMORY, "marginal index");
-          break;
-        }
-        int cus = 256;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, joint->device);
-        hipLaunchKernelGGL(freq_count_index_parts, dim3((unsigned)std::min<int64_t>(P, 2 * cus)), dim3(256), 0,
-                           mg->stream, mg->groups.p, mg->part_off.p, mg->part_groups.p, P, pbase[k].p,
-                           plog[k].p, cslots[k].p);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(mg->stream) != hipSuccess) {
-          res = fail(DQ_ERR_DEVICE, "marginal index");
-          break;
-        }
-        X[k] = CountIndex{cslots[k].p, 0, pbase[k].p, plog[k].p, 64 - kBucketBits - mg->s_bits};
-      } else {  // one table over the compacted groups
-        res = compact_groups(mg);
-        if (res != DQ_OK) break;
-        const int64_t m = mg->n_compact;
-        uint64_t cap = 2;
-        while (cap < (uint64_t)(2 * m)) cap <<= 1;
-        if (cslots[k].ensure(cap) != hipSuccess ||
-            hipMemsetAsync(cslots[k].p, 0, cap * sizeof(CountSlot), stream) != hipSuccess) {
-          res = fail(DQ_ERR_OUT_OF_MEMORY, "marginal index");
-          break;
-        }
-        if (m)
-          hipLaunchKernelGGL(freq_count_index, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream,
-                             mg->compact.p, m, cap - 1, cslots[k].p);
-        X[k] = CountIndex{cslots[k].p, cap - 1, nullptr, nullptr, 0};
-      }
-    } else {
-      res = compact_groups(marg[k]);
-      if (res != DQ_OK) break;
-      const int64_t m = marg[k]->n_compact;
-      uint64_t cap = 2;
-      while (cap < (uint64_t)(2 * m)) cap <<= 1;
-      if (slots[k].ensure(cap) != hipSuccess || hipMemsetAsync(slots[k].p, 0, cap * 4, stream) != hipSuccess) {
-        res = fail(DQ_ERR_OUT_OF_MEMORY, "marginal index");
-        break;
-      }
-      if (m)
-        hipLaunchKernelGGL(freq_lookup_build, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream,
-                           marg[k]->compact.p, m, cap - 1, slots[k].p);
-      L[k] = Lookup{marg[k]->compact.p, slots[k].p, cap - 1, arena_of(marg[k]), ty, marg[k]->exact ? 1 : 0,
-                    marg[k]->rec_var_base};
-    }
-    stamp(k ? "marginal 1 index" : "marginal 0 index");
-  }
-  if (res == DQ_OK) {
-    DevBuf<double> terms;
-    DevBuf<unsigned long long> partial;
-    constexpr int kSumBlocks = 1024;
-    if (terms.ensure(n) != hipSuccess || partial.ensure(3 * kSumBlocks) != hipSuccess) {
-      res = fail(DQ_ERR_OUT_OF_MEMORY, "MutualInformation terms");
-    } else {
-      if (by_hash) {
-        const uint64_t* kp[2];
-        int kst[2], kex[2];
-        for (int k = 0; k < 2; ++k) {
-          kp[k] = small[k] ? reinterpret_cast<const uint64_t*>(hk[k].p) : reinterpret_cast<const uint64_t*>(rec[k].p);
-          kst[k] = small[k] ? 1 : (int)(sizeof(RecIn) / 8);
-          kex[k] = small[k] ? 0 : (marg[k]->exact ? 1 : 0);
-        }
-        hipLaunchKernelGGL(freq_mi_terms_h, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
-                           joint->compact.p, n, kp[0], kst[0], kp[1], kst[1], kex[0], kex[1], X[0], X[1],
-                           (double)joint->num_rows, terms.p);
-      } else {
-        hipLaunchKernelGGL(freq_mi_terms, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
-                           joint->compact.p, n, arena_of(joint), part_types(joint, 1), L[0], L[1],
-                           (double)joint->num_rows, terms.p);
-      }
-      stamp("terms");
-      hipLaunchKernelGGL(freq_sum_fix, dim3(kSumBlocks), dim3(256), 0, stream, terms.p, n, partial.p);
-      std::vector<unsigned long long> h(3 * kSumBlocks);
-      if (hipGetLastError() != hipSuccess ||
-          d2h(h.data(), partial.p, 3 * kSumBlocks * 8, stream) != hipSuccess) {
-        res = fail(DQ_ERR_DEVICE, "MutualInformation launch failed");
-      } else {
-        fix128 sum = 0;
-        double nf = 0.0;
-        for (int b = 0; b < kSumBlocks; ++b) {
-          sum += (fix128)(((unsigned __int128)h[3 * b + 1] << 64) | h[3 * b]);
-          nf += __builtin_bit_cast(double, h[3 * b + 2]);
-        }
-        *mi = fix_to_f64(sum) + nf;
-      }
-    }
-  }
-  stamp("sum");
-  for (dq_freq* m : marg) dq_freq_destroy(m);
-  stamp("destroy");
-  return res;
-}
-
 // ---- HLL++ registers from a table's records (ApproxCountDistinct beside a grouping) ------------
 // The registers depend only on the set of distinct non-NULL values (StatefulHyperloglogPlus.scala:
 // 87-113: each value's XXH64, seed 42, raises one register; merges take the max), and raising a
@@ -7144,10 +5764,7 @@ static dq_status topk_recount(dq_freq* f, int k, FEntry* list, int64_t nb, std::
   int cus = 256;
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, f->device);
   const unsigned grid = (unsigned)std::min<int64_t>(nb, 2 * cus);
-  if (f->exact)
-    hipLaunchKernelGGL((freq_phaseC_x<false, false>), dim3(grid), dim3(kCThreads), 0, f->stream, a);
-  else
-    hipLaunchKernelGGL(freq_phaseC_h<false>, dim3(grid), dim3(kCThreads), 0, f->stream, a);
+  launch_phase_c(f, a, true, false, false, grid, grid);  // (whole partitions, as a first pass)
   HIP_TRY(hipGetLastError());
   unsigned int m = 0;
   HIP_TRY(d2h(&m, novf.p, 4, f->stream));
@@ -7363,11 +5980,6 @@ extern "C" dq_status dq_freq_partition(dq_freq* f, int n_parts, dq_freq_record* 
                        var, rec, var_n);
 }
 
-static dq_status add_records(dq_freq* f, const dq_freq_record* records, const uint8_t* var,
-                             int n_src, const int64_t* src_records, const int64_t* src_var_bytes,
-                             int64_t num_rows, const int64_t* special, int null_as_group,
-                             void* hip_stream, bool borrow);
-
 extern "C" dq_status dq_freq_add_records_device(dq_freq* f, const dq_freq_record* records,
                                                 const uint8_t* var, int n_src,
                                                 const int64_t* src_records,
@@ -7380,10 +5992,10 @@ extern "C" dq_status dq_freq_add_records_device(dq_freq* f, const dq_freq_record
 
 // borrow: read the var bytes in place (arena_view) instead of copying them into the table's
 // arena -- only for a fresh hashed table that dies before the var bytes do
-static dq_status add_records(dq_freq* f, const dq_freq_record* records, const uint8_t* var,
-                             int n_src, const int64_t* src_records, const int64_t* src_var_bytes,
-                             int64_t num_rows, const int64_t* special, int null_as_group,
-                             void* hip_stream, bool borrow) {
+dq_status dq::add_records(dq_freq* f, const dq_freq_record* records, const uint8_t* var,
+                          int n_src, const int64_t* src_records, const int64_t* src_var_bytes,
+                          int64_t num_rows, const int64_t* special, int null_as_group,
+                          void* hip_stream, bool borrow) {
   if (!f || !src_records || !src_var_bytes || !special)
     return fail(DQ_ERR_INVALID_ARGUMENT, "null argument");
   if (f->arena_view) return fail(DQ_ERR_STATE, "a table reading another table's keys takes no adds");
@@ -7413,10 +6025,7 @@ static dq_status add_records(dq_freq* f, const dq_freq_record* records, const ui
   a.segs.rec_start[n_src] = total_rec;
   if (total_rec && !records) return fail(DQ_ERR_INVALID_ARGUMENT, "null records");
   if (!f->exact && total_var && !var) return fail(DQ_ERR_INVALID_ARGUMENT, "null var bytes");
-  static const int dbg = [] {  // DQ_FREQ_DEBUG: the steps below, timed (synchronising)
-    const char* e = getenv("DQ_FREQ_DEBUG");
-    return e ? atoi(e) : 0;
-  }();
+  const int dbg = freq_debug_level();  // the steps below, timed (synchronising)
   auto t_last = std::chrono::steady_clock::now();
   auto stamp = [&](const char* what) {
     if (!dbg) return;
@@ -7499,44 +6108,6 @@ static dq_status add_records(dq_freq* f, const dq_freq_record* records, const ui
 // which adds counts of equal keys (duplicate entries) and keeps equal hashes with different keys
 // apart.  An entry is hashed and encoded once, not once per row.
 // ------------------------------------------------------------------------------------------------
-namespace dq {
-
-// words: [0] records written, [1] var bytes written, [2] rows of NULL entries, [3] rows whose NaN
-// payload the Histogram mode folded (C_NAN_FOLDED, as the row path counts it)
-__global__ void __launch_bounds__(256)
-freq_dict_records(KeySet ks, int exact, int64_t entries, const unsigned long long* __restrict__ counts,
-                  RecIn* __restrict__ recs, uint8_t* __restrict__ var,
-                  unsigned long long* __restrict__ words) {
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < entries; e += (int64_t)gridDim.x * 256) {
-    const unsigned long long c = counts[e];
-    if (!c) continue;
-    if (!kbit(ks.cols[0].valid, e)) {
-      atomicAdd(words + 2, c);
-      continue;
-    }
-    RecIn r;
-    r.count = c;
-    r.enc_off = 0;
-    if (exact) {
-      const uint64_t raw = kwiden(ks.cols[0].type, ks.cols[0].values, e);
-      r.key = exact_canon(ks, raw);
-      if (r.key != raw) atomicAdd(words + 3, c);
-    } else {  // (one key and hashed: a utf8 key)
-      const SView v = str1_view(ks, e);
-      const uint32_t enc = str1_enc_size(ks, e), sz = (enc + 7u) & ~7u;
-      const unsigned long long at = atomicAdd(words + 1, (unsigned long long)sz);
-      uint32_t* dst = reinterpret_cast<uint32_t*>(var + at);
-      str1_encode(ks, e, dst);
-      if (sz != enc) dst[enc / 4] = 0;
-      r.key = str_row_hash(v);
-      r.enc_off = at;
-    }
-    recs[atomicAdd(words, 1ull)] = r;
-  }
-}
-
-}  // namespace dq
-
 extern "C" dq_status dq_freq_add_dict_device(dq_freq* f, const dq_column* indices, int index_type,
                                              const dq_column* dictionary, int null_as_group,
                                              void* hip_stream) {
@@ -7615,164 +6186,5 @@ extern "C" dq_status dq_freq_add_dict_device(dq_freq* f, const dq_column* indice
     f->h_counters[C_NAN_FOLDED] += w[3];
     return push_counters(f);
   }
-  return DQ_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Multi-GPU raw-key repartition: a one-column fixed-width key of high
-// cardinality (a unique id) is exchanged as its raw values, before any local count -- one
-// group-by per row on its owner rank and 1-8 bytes per row over xGMI, instead of a local group-by,
-// 24-byte records and a second group-by.  The owner is a function of the key the table counts
-// (fmix of the canonical widened value, freq_codec.h), so every rank sends equal keys to one owner;
-// NULL rows stay home as a count.
-// ------------------------------------------------------------------------------------------------
-namespace dq {
-
-constexpr int kKeyPartThreads = 256;
-constexpr int kKeyPartRows = 16 * kKeyPartThreads;  // rows per block step
-
-DQ_DEV uint32_t raw_owner(int type, const void* values, int64_t r, int null_as_group, int parts) {
-  KeySet ks;
-  ks.n_keys = 1;
-  ks.null_as_group = null_as_group;
-  ks.cols[0].type = type;
-  const uint64_t h = fmix_bij(exact_canon(ks, kwiden(type, values, r)));
-  return (uint32_t)(((h & 0xFFFFFFULL) * (uint64_t)parts) >> 24);  // low bits: the owner's keys
-                                                                   // still fill every bucket
-}
-
-__global__ void __launch_bounds__(kKeyPartThreads)
-key_owner_count(int type, const uint8_t* __restrict__ valid, const void* __restrict__ values,
-                int64_t rows, int null_as_group, int parts, unsigned long long* __restrict__ counts,
-                unsigned long long* __restrict__ nulls) {
-  __shared__ uint32_t s_cnt[kMaxParts];
-  for (int i = threadIdx.x; i < parts; i += kKeyPartThreads) s_cnt[i] = 0;
-  __syncthreads();
-  unsigned long long nn = 0;
-  for (int64_t r = (int64_t)blockIdx.x * kKeyPartThreads + threadIdx.x; r < rows;
-       r += (int64_t)gridDim.x * kKeyPartThreads) {
-    if (!kbit(valid, r)) {
-      ++nn;
-      continue;
-    }
-    atomicAdd(&s_cnt[raw_owner(type, values, r, null_as_group, parts)], 1u);
-  }
-  nn = wave_sum(nn);
-  if (__lane_id() == 0 && nn) atomicAdd(nulls, nn);
-  __syncthreads();
-  for (int i = threadIdx.x; i < parts; i += kKeyPartThreads)
-    if (s_cnt[i]) atomicAdd(&counts[i], (unsigned long long)s_cnt[i]);
-}
-
-// Each block step of kKeyPartRows rows counts its rows per owner in LDS, reserves its run in every
-// owner segment with one atomic per owner, then writes every row's value into its run (the runs of
-// a step are contiguous per owner, so the stores of a wave land in a few neighbouring lines).
-__global__ void __launch_bounds__(kKeyPartThreads)
-key_owner_scatter(int type, int elem, const uint8_t* __restrict__ valid,
-                  const void* __restrict__ values, int64_t rows, int null_as_group, int parts,
-                  unsigned long long* __restrict__ cursor, uint8_t* __restrict__ out) {
-  __shared__ uint32_t s_cnt[kMaxParts], s_pos[kMaxParts];
-  __shared__ unsigned long long s_base[kMaxParts];
-  for (int64_t r0 = (int64_t)blockIdx.x * kKeyPartRows; r0 < rows;
-       r0 += (int64_t)gridDim.x * kKeyPartRows) {
-    for (int i = threadIdx.x; i < parts; i += kKeyPartThreads) s_cnt[i] = s_pos[i] = 0;
-    __syncthreads();
-    uint32_t own[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      const int64_t r = r0 + (int64_t)k * kKeyPartThreads + threadIdx.x;
-      own[k] = ~0u;
-      if (r < rows && kbit(valid, r)) {
-        own[k] = raw_owner(type, values, r, null_as_group, parts);
-        atomicAdd(&s_cnt[own[k]], 1u);
-      }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < parts; i += kKeyPartThreads)
-      s_base[i] = s_cnt[i] ? atomicAdd(&cursor[i], (unsigned long long)s_cnt[i]) : 0ULL;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      if (own[k] == ~0u) continue;
-      const int64_t r = r0 + (int64_t)k * kKeyPartThreads + threadIdx.x;
-      const uint64_t at = s_base[own[k]] + atomicAdd(&s_pos[own[k]], 1u);
-      const uint8_t* src = reinterpret_cast<const uint8_t*>(values) + r * elem;
-      uint8_t* dst = out + at * elem;
-      switch (elem) {
-        case 1: *dst = *src; break;
-        case 2: *reinterpret_cast<uint16_t*>(dst) = *reinterpret_cast<const uint16_t*>(src); break;
-        case 4: *reinterpret_cast<uint32_t*>(dst) = *reinterpret_cast<const uint32_t*>(src); break;
-        default: *reinterpret_cast<uint64_t*>(dst) = *reinterpret_cast<const uint64_t*>(src); break;
-      }
-    }
-    __syncthreads();  // s_cnt / s_pos / s_base are reset by the next step
-  }
-}
-
-}  // namespace dq
-
-static int raw_key_elem(int type) {
-  switch (type) {
-    case DQ_INT8: return 1;
-    case DQ_INT16: return 2;
-    case DQ_INT32: case DQ_FLOAT32: return 4;
-    case DQ_INT64: case DQ_FLOAT64: return 8;
-    default: return 0;  // bool (bit-packed) and strings: the records path
-  }
-}
-
-extern "C" dq_status dq_key_partition(const dq_column* batches, int n_batches, int n_parts,
-                                      int null_as_group, uint8_t* out, int64_t* counts_out,
-                                      int64_t* null_rows_out, void* hip_stream) {
-  using namespace dq;
-  if ((n_batches > 0 && !batches) || n_batches < 0 || !counts_out || !null_rows_out)
-    return fail(DQ_ERR_INVALID_ARGUMENT, "null argument");
-  if (n_parts < 1 || n_parts > kMaxParts)
-    return fail(DQ_ERR_UNSUPPORTED, "n_parts must be in [1, %d]", kMaxParts);
-  int64_t rows = 0;
-  const int ltype = n_batches ? batches[0].type : DQ_INT64;
-  // a date / timestamp key is its int32 / int64 (equal keys, equal owner, as a table counts them)
-  const int type = ltype == DQ_DATE32 ? DQ_INT32 : ltype == DQ_TIMESTAMP_US ? DQ_INT64 : ltype;
-  const int elem = raw_key_elem(type);
-  if (!elem) return fail(DQ_ERR_WRONG_TYPE, "raw-key repartition needs a fixed-width key");
-  for (int b = 0; b < n_batches; ++b) {
-    if (batches[b].type != ltype) return fail(DQ_ERR_WRONG_TYPE, "batches differ in type");
-    if (batches[b].length < 0 || (batches[b].length && !batches[b].values))
-      return fail(DQ_ERR_INVALID_ARGUMENT, "batch %d has no values", b);
-    rows += batches[b].length;
-  }
-  if (rows && !out) return fail(DQ_ERR_INVALID_ARGUMENT, "null output buffer");
-  hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
-  DevBuf<unsigned long long> cnt;
-  HIP_TRY(cnt.ensure(2 * kMaxParts + 1));
-  HIP_TRY(hipMemsetAsync(cnt.p, 0, (2 * kMaxParts + 1) * 8, stream));
-  for (int b = 0; b < n_batches; ++b) {
-    const dq_column& c = batches[b];
-    if (!c.length) continue;
-    const unsigned grid = (unsigned)std::min<int64_t>((c.length + kKeyPartRows - 1) / kKeyPartRows * 4, 4096);
-    hipLaunchKernelGGL(key_owner_count, dim3(grid), dim3(kKeyPartThreads), 0, stream, type,
-                       c.validity, c.values, c.length, null_as_group, n_parts, cnt.p,
-                       cnt.p + 2 * kMaxParts);
-    HIP_TRY(hipGetLastError());
-  }
-  unsigned long long h[2 * kMaxParts + 1];
-  HIP_TRY(d2h(h, cnt.p, sizeof(h), stream));
-  unsigned long long base = 0;
-  for (int j = 0; j < n_parts; ++j) {  // segment cursors: the exclusive prefix of the counts
-    counts_out[j] = (int64_t)h[j];
-    h[kMaxParts + j] = base;
-    base += h[j];
-  }
-  *null_rows_out = (int64_t)h[2 * kMaxParts];
-  HIP_TRY(hipMemcpyAsync(cnt.p + kMaxParts, h + kMaxParts, kMaxParts * 8, hipMemcpyHostToDevice, stream));
-  for (int b = 0; b < n_batches; ++b) {
-    const dq_column& c = batches[b];
-    if (!c.length) continue;
-    const unsigned grid = (unsigned)std::min<int64_t>((c.length + kKeyPartRows - 1) / kKeyPartRows, 4096);
-    hipLaunchKernelGGL(key_owner_scatter, dim3(grid), dim3(kKeyPartThreads), 0, stream, type, elem,
-                       c.validity, c.values, c.length, null_as_group, n_parts, cnt.p + kMaxParts, out);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipStreamSynchronize(stream));  // the cursors' buffer dies here
   return DQ_OK;
 }

@@ -245,9 +245,10 @@ DQ_HD uint64_t row_hash_hashed(const KeySet& ks, int64_t r) {
 // The row hash of a one-column utf8 key (row_hash_hashed with n_keys == 1).
 DQ_HD uint64_t str_row_hash(const SView& v) { return fmix_bij(fold_col_hash(kRowHashSeed, str_col_hash(v, 0))); }
 // The same, out of line, for phase A's strings longer than 16 bytes (rare in a wave; one copy of
-// the XXH64 loop instead of one per unrolled round)
-__host__ __device__ __attribute__((noinline)) uint64_t str_row_hash_long(const uint8_t* p,
-                                                                         int32_t len) {
+// the XXH64 loop instead of one per unrolled round; `inline` for the linker: several units
+// include this header)
+inline __host__ __device__ __attribute__((noinline)) uint64_t str_row_hash_long(const uint8_t* p,
+                                                                                int32_t len) {
   return str_row_hash(SView{p, len});
 }
 // The same for a non-NULL string of len <= 16 bytes already in registers.
@@ -557,7 +558,7 @@ __device__ inline void str1_encode_copy16(const uint8_t* p, int32_t len, uint32_
 #endif
 
 // (out of line: only long strings get here, so one copy instead of one per call site)
-__host__ __device__ __attribute__((noinline)) bool str1_rows_equal(const KeySet& ks, int64_t r1,
+inline __host__ __device__ __attribute__((noinline)) bool str1_rows_equal(const KeySet& ks, int64_t r1,
                                                                    int64_t r2) {
   const SView a = str1_view(ks, r1), b = str1_view(ks, r2);
   return a.len == b.len && bytes_equal(a.p, b.p, a.len);

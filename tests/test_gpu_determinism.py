@@ -2,7 +2,7 @@
 
 Entropy (-p ln p per group) and MutualInformation (p ln(p / (px py)) per joint group) are sums of
 per-group fp64 terms.  The engine adds the terms as 128-bit fixed-point integers at 2^-112
-(freq.hip fix_of: exact for every term >= 2^-60), so the sum does not depend on the order the
+(freq_device.h fix_of: exact for every term >= 2^-60), so the sum does not depend on the order the
 groups are met in.  Contract, asserted here:
   * bit-identical across runs on freshly built tables, across batchings of the same rows, across
     partition depths (DQ_FREQ_PARTITION_TARGET: the sub-bucket bits) and the recount path of
