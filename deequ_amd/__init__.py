@@ -13,5 +13,11 @@ from .checks import Check, CheckLevel, CheckResult, CheckStatus, ConstraintStatu
 from .verification import VerificationResult, VerificationSuite  # noqa: F401
 from .schema import (RowLevelSchema, RowLevelSchemaValidationResult,  # noqa: F401
                      RowLevelSchemaValidator, SchemaValueNotSupported)
+from .suggestions import (CategoricalRangeRule, CompleteIfCompleteRule,  # noqa: F401
+                          ConstraintRule, ConstraintSuggestion, ConstraintSuggestionResult,
+                          ConstraintSuggestionRunBuilder, ConstraintSuggestionRunner,
+                          ConstraintSuggestions, FractionalCategoricalRangeRule,
+                          NonNegativeNumbersRule, PositiveNumbersRule, RetainCompletenessRule,
+                          RetainTypeRule, Rules, UniqueIfApproximatelyUniqueRule)
 
 __version__ = "0.1.0"

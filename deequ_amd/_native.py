@@ -114,6 +114,7 @@ class dq_freq_summary(Structure):
 # dq_schema_kind
 SCHEMA_STRING, SCHEMA_INT, SCHEMA_DECIMAL, SCHEMA_TIMESTAMP = range(1, 5)
 SELECT_TILE_ROWS = 16384  # DQ_SELECT_TILE_ROWS
+SPLIT_MAX = 8  # DQ_SPLIT_MAX
 
 
 class dq_schema_column(Structure):
@@ -207,6 +208,8 @@ def _load() -> ctypes.CDLL:
                                      c_void_p]),
         "dq_dict_decode": (c_int, [POINTER(dq_column), c_int, POINTER(dq_column), POINTER(dq_column),
                                    POINTER(c_int64), c_void_p]),
+        "dq_split_rows": (c_int, [c_int64, c_int64, c_uint64, POINTER(c_double), c_int,
+                                  POINTER(c_void_p), POINTER(c_int64), c_void_p]),
         "dq_freq_add_dict_device": (c_int, [c_void_p, POINTER(dq_column), c_int, POINTER(dq_column),
                                             c_int, c_void_p]),
         "dq_freq_import": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
@@ -259,7 +262,7 @@ EXPORTED = [
     "dq_freq_add_host", "dq_freq_partition_sizes", "dq_freq_partition",
     "dq_freq_add_records_device", "dq_key_partition",
     "dq_schema_evaluate", "dq_select_plan", "dq_gather_column",
-    "dq_dict_decode", "dq_freq_add_dict_device",
+    "dq_dict_decode", "dq_freq_add_dict_device", "dq_split_rows",
 ]
 FREQ_RECORD_BYTES = 24  # sizeof(dq_freq_record)
 

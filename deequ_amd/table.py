@@ -203,6 +203,85 @@ class Table:
             out.append({f.name: _empty_column(f.dtype, self.device) for f in self.schema.fields})
         return Table(self.schema, out, self.device)
 
+    def random_split(self, weights: Sequence[float], seed: Optional[int] = None,
+                     stage_timer=None) -> List["Table"]:
+        """DataFrame.randomSplit(weights, seed): one table per weight, each row in exactly one of
+        them, with probability weight / sum(weights); row order and schema are kept.  A row's split
+        is a function of `seed` and its index in the table alone (dq_split_rows), so it does not
+        depend on the batches.  It is NOT Spark's draw.  `seed`: an int in
+        [-2^63, 2^64), taken mod 2^64 (Spark's seed is a signed Long); None draws one.  A
+        dictionary column's splits hold the decoded column, without the encoded pair.
+        stage_timer (tools/bench_split.py): as in RowLevelSchemaValidator.validate."""
+        import contextlib
+        import ctypes
+        import math
+        import numbers
+
+        import torch
+
+        from .schema import MAX_BATCH_ROWS, _alloc, gather_column, select_plan
+        timer = stage_timer or (lambda name: contextlib.nullcontext())
+        weights = list(weights)
+        if not 1 <= len(weights) <= N.SPLIT_MAX:
+            raise ValueError(f"random_split: {len(weights)} weights (1 .. {N.SPLIT_MAX})")
+        for w in weights:
+            if isinstance(w, bool) or not isinstance(w, numbers.Real) or not math.isfinite(w) or w <= 0:
+                raise ValueError(f"random_split: weight {w!r} is not a positive finite number")
+        if seed is None:
+            import random
+            seed = random.SystemRandom().getrandbits(64)
+        if isinstance(seed, bool) or not isinstance(seed, int) or not -2**63 <= seed < 2**64:
+            raise ValueError(f"random_split: seed {seed!r} is not an int in [-2^63, 2^64)")
+        seed %= 2**64
+        # cumsum(w) / sum(w), in that order, the last forced to 1
+        acc, cum = 0.0, []
+        for w in weights:
+            acc += float(w)
+            cum.append(acc)
+        bounds = [c / acc for c in cum]
+        bounds[-1] = 1.0
+        k = len(weights)
+        fields = self.schema.fields
+        for b in self.batches:
+            for f in fields:
+                if b[f.name].stand_in:
+                    raise ValueError(f"column {f.name} is {f.type_name}: its rows cannot be selected")
+                if b[f.name].length > MAX_BATCH_ROWS:
+                    raise ValueError(f"column {f.name}: a batch of {b[f.name].length} rows "
+                                     f"(at most {MAX_BATCH_ROWS})")
+        out: List[List[Dict[str, ColumnBatch]]] = [[] for _ in range(k)]
+        cbounds = (ctypes.c_double * k)(*bounds)
+        row_base = 0
+        with torch.cuda.device(self.device):
+            stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            for b in self.batches:
+                rows = b[fields[0].name].length if fields else 0
+                if rows == 0:
+                    continue
+                cols = [b[f.name] for f in fields]
+                utf8 = [c for c in cols if N.type_id(c.dtype) == N.UTF8]
+                bitmaps = [_alloc((rows + 63) // 64 * 8, self.device) for _ in range(k)]
+                ptrs = (ctypes.c_void_p * k)(*[t.data_ptr() for t in bitmaps])
+                counts = (ctypes.c_int64 * k)()
+                with timer("split"):
+                    N.check(N.lib.dq_split_rows(rows, row_base, seed, cbounds, k, ptrs, counts,
+                                                stream))
+                for s in range(k):
+                    if counts[s] == 0:
+                        continue
+                    with timer("select"):
+                        index, n_sel, nbytes = select_plan(bitmaps[s], rows, utf8, self.device,
+                                                           stream, counts[s])
+                    assert n_sel == counts[s], (n_sel, counts[s])
+                    sizes = iter(nbytes)
+                    with timer("gather"):
+                        out[s].append({f.name: gather_column(
+                            c, index, n_sel, next(sizes) if N.type_id(c.dtype) == N.UTF8 else 0,
+                            self.device, stream) for f, c in zip(fields, cols)})
+                row_base += rows
+        return [Table(self.schema, batches, self.device) if batches
+                else Table(self.schema, [], self.device).select_rows(0, 0) for batches in out]
+
     # -------------------------------------------------------------------------------------------
     # construction
     # -------------------------------------------------------------------------------------------

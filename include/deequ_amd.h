@@ -661,6 +661,30 @@ dq_status dq_select_plan(const uint64_t* bitmap, int64_t rows, int32_t* index_ou
 dq_status dq_gather_column(const dq_column* in, const int32_t* index, int64_t n_out,
                            dq_column* out, void* hip_stream);
 
+/* Most splits of one dq_split_rows call. */
+#define DQ_SPLIT_MAX 8
+
+/* Assigns each row of one batch to one of n_splits splits (1 .. DQ_SPLIT_MAX): the device side of
+ * data.randomSplit (ConstraintSuggestionRunner.scala:80-92).  The draw depends only on `seed` and
+ * the row's table-global index r = row_base + (row in batch), so a split does not depend on how a
+ * table was cut into batches:
+ *   z = seed + (r + 1) * 0x9E3779B97F4A7C15                  (mod 2^64)
+ *   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *   z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *   z =  z ^ (z >> 31)
+ *   u = (z >> 11) * 2^-53                                     (fp64, exact)
+ *   split(r) = the first k with u < bounds[k]
+ * bounds[n_splits] (host memory) are the normalised cumulative weights: non-decreasing, in
+ * (0, 1], the last exactly 1 (anything else: DQ_ERR_INVALID_ARGUMENT, as are a negative rows or
+ * row_base and null pointers; more than 2^31-1 rows: DQ_ERR_UNSUPPORTED).  bitmaps[n_splits] (a
+ * host array) names n_splits device bitmaps of (rows + 63) / 64 uint64 words in dq_select_plan's
+ * layout: on return exactly one of them has bit i set for every i < rows, and the bits at and
+ * beyond rows in the last word are zero.  counts[n_splits] (host memory) are the bitmaps'
+ * popcounts; they sum to rows.  rows == 0 launches nothing (the bitmaps may then be NULL).  One
+ * launch; waits for `hip_stream`. */
+dq_status dq_split_rows(int64_t rows, int64_t row_base, uint64_t seed, const double* bounds,
+                        int n_splits, uint64_t* const* bitmaps, int64_t* counts, void* hip_stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Dictionary-encoded columns (Arrow dictionary<I, V>): the dictionary is an ordinary dq_column of
  * V; the indices travel as a dq_column whose `values` are `length` integers of the width and
