@@ -199,6 +199,7 @@ def _load() -> ctypes.CDLL:
         "dq_decimal_to_double": (c_double, [c_uint64, c_int64, c_int32]),
         "dq_format_values": (c_int, [c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
         "dq_cast_utf8": (c_int, [POINTER(dq_column), c_int, c_void_p, c_void_p, POINTER(c_int64), c_void_p]),
+        "dq_cast_parse_utf8": (c_int, [c_char_p, c_int32, c_int, POINTER(c_int64), POINTER(c_double)]),
         "dq_schema_evaluate": (c_int, [POINTER(dq_schema_column), c_int, POINTER(dq_column), c_int,
                                        c_int64, c_void_p, c_void_p, POINTER(c_int64),
                                        POINTER(c_int64), POINTER(c_int64), c_void_p]),
@@ -254,7 +255,7 @@ EXPORTED = [
     "dq_state_destroy", "dq_state_reset", "dq_scan_device", "dq_scan_device_batches",
     "dq_state_sync", "dq_state_get", "dq_state_get_all", "dq_state_merge", "dq_state_serialized_size",
     "dq_state_serialize", "dq_state_deserialize", "dq_hll_count", "dq_xxhash64", "dq_column_release", "dq_java_double_to_string", "dq_java_float_to_string", "dq_java_doubles_to_strings", "dq_freq_create",
-    "dq_freq_destroy", "dq_freq_reset", "dq_freq_add_device", "dq_freq_summarize", "dq_freq_summarize_keys", "dq_sorted_sample", "dq_freq_marginal", "dq_freq_mutual_information", "dq_freq_num_groups", "dq_freq_null_literal", "dq_freq_import", "dq_cast_utf8", "dq_release_cached_memory", "dq_cached_device_bytes", "dq_freq_hll", "dq_freq_folded_nan_rows",
+    "dq_freq_destroy", "dq_freq_reset", "dq_freq_add_device", "dq_freq_summarize", "dq_freq_summarize_keys", "dq_sorted_sample", "dq_freq_marginal", "dq_freq_mutual_information", "dq_freq_num_groups", "dq_freq_null_literal", "dq_freq_import", "dq_cast_utf8", "dq_cast_parse_utf8", "dq_release_cached_memory", "dq_cached_device_bytes", "dq_freq_hll", "dq_freq_folded_nan_rows",
     "dq_state_exchange_sizes", "dq_state_exchange_pack", "dq_state_exchange_unpack",
     "dq_host_wait_count", "dq_decimal_to_double", "dq_format_values",
     "dq_freq_num_rows", "dq_freq_export", "dq_freq_merge", "dq_freq_topk", "dq_loader_create",
@@ -314,6 +315,14 @@ def java_float_to_string(f: float) -> str:
     buf = ctypes.create_string_buffer(32)
     n = lib.dq_java_float_to_string(f, buf)
     return buf.raw[:n].decode("ascii")
+
+
+def cast_parse_utf8(text: bytes, to_type: int) -> tuple:
+    """dq_cast_utf8's verdict on one string -- (0 NULL | 1 value | 2 unsupported, the value or
+    None) -- from the parsers the device kernel calls (cast_parse.h), run on the host."""
+    lv, dv = c_int64(0), c_double(0.0)
+    res = lib.dq_cast_parse_utf8(text, len(text), to_type, ctypes.byref(lv), ctypes.byref(dv))
+    return res, (None if res != 1 else lv.value if to_type == INT64 else dv.value)
 
 
 def release_cached_memory() -> None:

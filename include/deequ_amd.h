@@ -565,13 +565,29 @@ int64_t dq_cached_device_bytes(int device);
 /* Spark 2.2 Cast(StringType -> LongType | DoubleType) of a utf8 column, on the device: the
  * ColumnProfiler's cast of string columns inferred numeric (profiles/ColumnProfiler.scala:311-320,
  * 389-405).  to_type DQ_INT64 follows UTF8String.toLong (sign, digits, '.' + digits truncated);
- * DQ_FLOAT64 follows java.lang.Double.parseDouble over decimal strings.  A string that does not
- * convert is NULL in validity_out (LSB-first, (length + 7) / 8 bytes); values_out holds length
- * int64 / double.  *n_unsupported counts strings parseDouble would read that are not converted
- * here exactly (exponents, NaN/Infinity, hex, > 19 significant digits ...): those rows are NULL and
- * the caller must treat a non-zero count as a failure.  Synchronises `hip_stream`. */
+ * DQ_FLOAT64 follows java.lang.Double.parseDouble.  Every row has one of three results:
+ *   value        the converted number (validity bit 1).  For DQ_FLOAT64 at least every plain
+ *                decimal (bytes <= ' ' trimmed, optional sign, digits with at most one '.', no
+ *                exponent or suffix) whose digits without leading and trailing zeros are d <= 2^53
+ *                and whose matching power of ten e has |e| <= 22, or e > 22 with
+ *                d * 10^(e - 22) <= 2^53; zero in any spelling.  The result is the double nearest
+ *                to the decimal, the sign of zero kept.
+ *   NULL         Spark's NULL (validity bit 0): toLong returns false / parseDouble throws
+ *                NumberFormatException, decided by the grammar of Double.valueOf's documentation
+ *                ("1e", "d", "0x1", "1d2" are NULL like "abc").  A NULL input row stays NULL.
+ *   unsupported  DQ_FLOAT64 only: parseDouble reads the string but it is not converted here (an
+ *                exponent, NaN / Infinity, a hex form, an f/F/d/D suffix, a plain decimal outside
+ *                the window above).  The row is NULL and counted in *n_unsupported; the caller must
+ *                treat a non-zero count as a failure.
+ * validity_out holds (length + 7) / 8 bytes, LSB-first, the bits past the last row zero; values_out
+ * holds length int64 / double, 0 wherever the validity bit is 0.  Synchronises `hip_stream`. */
 dq_status dq_cast_utf8(const dq_column* in, int to_type, void* values_out, uint8_t* validity_out,
                        int64_t* n_unsupported, void* hip_stream);
+/* dq_cast_utf8's verdict on one string of n bytes, computed on the host by the functions the
+ * device kernel calls: 0 = NULL, 1 = value (in *long_out for DQ_INT64, else in *double_out),
+ * 2 = unsupported.  The output that is written holds 0 unless the result is 1. */
+int dq_cast_parse_utf8(const uint8_t* s, int32_t n, int to_type, int64_t* long_out,
+                       double* double_out);
 
 /* ------------------------------------------------------------------------------------------------
  * Row-level schema validation (schema/RowLevelSchemaValidator.scala:183-281) and the row selection
