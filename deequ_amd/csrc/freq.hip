@@ -3636,7 +3636,10 @@ __global__ void __launch_bounds__(kCThreads, 4) freq_phaseC_h(CArgs a) {
       for (int q = 0; q < PF; ++q) {
         h[q] = w[q][0];
         const uint64_t c = code_count((uint32_t)(w[q][1] & 0xff));
-        v[q] = ((w[q][1] >> 8) << 24) | c;  // rep << 24 | count
+        // rep << 24 | count.  A count the field cannot hold hands the item on (below); it is
+        // kept out of v, where a digit of 2^24 or more (a record of a repartitioned or imported
+        // table) would change rep, the arena offset the key comparison reads from
+        v[q] = ((w[q][1] >> 8) << 24) | (c < (1u << 12) ? c : 1ULL);
         slot[q] = (uint32_t)h[q] & (KT - 1);
         step[q] = ((uint32_t)(h[q] >> 40) | 1u) & (KT - 1);
         const bool in = (valid >> q) & 1u;
@@ -6004,6 +6007,8 @@ dq_status dq::add_records(dq_freq* f, const dq_freq_record* records, const uint8
     return fail(DQ_ERR_STATE, "only a fresh hashed table can borrow var bytes");
   if (n_src < 1 || n_src > kMaxParts)
     return fail(DQ_ERR_UNSUPPORTED, "n_src must be in [1, %d]", kMaxParts);
+  // (refused before anything is inserted: a refused call leaves the table as it was)
+  if (special[0]) return fail(DQ_ERR_INVALID_ARGUMENT, "special[0] is no longer used (must be 0)");
   const int mode = null_as_group ? 1 : 0;
   if (f->mode_null_as_group >= 0 && f->mode_null_as_group != mode)
     return fail(DQ_ERR_STATE, "null_as_group must be the same for every batch");
@@ -6095,7 +6100,6 @@ dq_status dq::add_records(dq_freq* f, const dq_freq_record* records, const uint8
   }
   f->h_counters[C_NULL_GROUP] += (uint64_t)special[1];
   f->h_counters[C_NULL_ROWS] += (uint64_t)special[2];
-  if (special[0]) return fail(DQ_ERR_INVALID_ARGUMENT, "special[0] is no longer used (must be 0)");
   f->num_rows += num_rows;
   return push_counters(f);
 }

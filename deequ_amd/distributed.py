@@ -443,28 +443,73 @@ def _raw_keys_pay(data_shard, column, dtype) -> bool:
     return r > 0 and g >= RAW_MIN_DISTINCT * r
 
 
-def raw_key_repartition(data_shard, column, dtype, null_as_group: bool = False):
-    """The Exchange of a high-cardinality one-column fixed-width key as raw values: every rank cuts
-    its rows into owner segments on the device (dq_key_partition), the segments meet in one
-    all-to-all (1-8 bytes per row over xGMI), and each owner counts what it received in ONE
-    group-by.  NULL rows stay home as counts; numRows and the NULL counts are summed in one
-    all-reduce and the NULL group lives on rank 0, as in freq_repartition."""
+def raw_key_partition(data_shard, column, dtype, world: int, null_as_group: bool = False,
+                      out=None):
+    """raw_key_repartition before its first collective: this rank's non-NULL values of `column`
+    cut into `world` owner segments on the device (dq_key_partition).  Returns (out, counts,
+    nulls): `out` a uint8 device tensor holding the segments back to back, owner j's at the
+    exclusive prefix of counts[0..world) elements of RAW_KEY_ELEM[dtype] bytes; `nulls` the NULL
+    rows, which stay home.  `out`: a caller's buffer of at least rows x element size bytes."""
     import torch
-    import torch.distributed as dist
-    from .analyzers.grouping import FrequencyTable
-    from .table import ColumnBatch
-    world, rank = dist.get_world_size(), dist.get_rank()
     dev = f"cuda:{data_shard.device_index()}"
     elem = RAW_KEY_ELEM[dtype]
     cols = [b[column] for b in data_shard.batches]
     rows = sum(c.length for c in cols)
     arr = (N.dq_column * max(1, len(cols)))(*[c.to_c() for c in cols])
-    out = torch.empty(max(1, rows * elem), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty(max(1, rows * elem), dtype=torch.uint8, device=dev)
+    elif out.numel() < rows * elem:
+        raise ValueError(f"raw-key buffer of {out.numel()} bytes for {rows} rows of {elem} bytes")
     counts = np.zeros(world, np.int64)
     nulls = ctypes.c_int64()
     stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     N.check(N.lib.dq_key_partition(arr, len(cols), world, 1 if null_as_group else 0,
                                    out.data_ptr(), counts.ctypes.data, ctypes.byref(nulls), stream))
+    return out, counts, int(nulls.value)
+
+
+def raw_key_count(recv, n_recv: int, column, dtype, device_index: int, rank: int, world: int,
+                  tot_rows: int, tot_nulls: int, null_as_group: bool = False):
+    """raw_key_repartition after its last collective: owner `rank` of `world` counts the n_recv
+    values it received (`recv`, a uint8 device tensor) in one group-by; the rows that did not
+    travel (the NULL rows, and every other owner's) reach numRows, and the NULL rows rank 0's
+    outside-table counts, through a records call without records."""
+    import torch
+    from .analyzers.grouping import FrequencyTable
+    from .table import ColumnBatch
+    if not 0 <= rank < world:
+        raise ValueError(f"rank {rank} of {world}")
+    elem = RAW_KEY_ELEM[dtype]
+    owned = FrequencyTable([column], [dtype], device_index, capacity_hint=n_recv)
+    step = 1 << 26
+    for lo in range(0, n_recv, step):
+        m = min(step, n_recv - lo)
+        owned.add([ColumnBatch(dtype, m, None, recv[lo * elem: (lo + m) * elem])],
+                  null_as_group=null_as_group)
+    special = np.zeros(3, np.int64)
+    if rank == 0:
+        special[1 if null_as_group else 2] = tot_nulls
+    zero = np.zeros(1, np.int64)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(f"cuda:{device_index}").cuda_stream)
+    N.check(N.lib.dq_freq_add_records_device(
+        owned.handle, None, None, 1, zero.ctypes.data, zero.ctypes.data, tot_rows - n_recv,
+        special.ctypes.data, 1 if null_as_group else 0, stream))
+    return owned
+
+
+def raw_key_repartition(data_shard, column, dtype, null_as_group: bool = False):
+    """The Exchange of a high-cardinality one-column fixed-width key as raw values: every rank cuts
+    its rows into owner segments on the device (raw_key_partition), the segments meet in one
+    all-to-all (1-8 bytes per row over xGMI), and each owner counts what it received in ONE
+    group-by (raw_key_count).  NULL rows stay home as counts; numRows and the NULL counts are
+    summed in one all-reduce and the NULL group lives on rank 0, as in freq_repartition."""
+    import torch
+    import torch.distributed as dist
+    world, rank = dist.get_world_size(), dist.get_rank()
+    dev = f"cuda:{data_shard.device_index()}"
+    elem = RAW_KEY_ELEM[dtype]
+    rows = sum(b[column].length for b in data_shard.batches)
+    out, counts, nulls = raw_key_partition(data_shard, column, dtype, world, null_as_group)
     cdev = _comm_device(dev)
     sizes = torch.from_numpy(counts.copy()).to(cdev)
     got = torch.empty_like(sizes)
@@ -480,24 +525,12 @@ def raw_key_repartition(data_shard, column, dtype, null_as_group: bool = False):
     recv = recv.to(dev)
     del out, sent
     n_recv = int(src.sum())
-    owned = FrequencyTable([column], [dtype], data_shard.device_index(), capacity_hint=n_recv)
-    step = 1 << 26
-    for lo in range(0, n_recv, step):
-        m = min(step, n_recv - lo)
-        owned.add([ColumnBatch(dtype, m, None, recv[lo * elem: (lo + m) * elem])],
-                  null_as_group=null_as_group)
-    tot = torch.tensor([rows, nulls.value], dtype=torch.int64, device=cdev)
+    tot = torch.tensor([rows, nulls], dtype=torch.int64, device=cdev)
     dist.all_reduce(tot)
     _count_reduce(tot)
     tot_rows, tot_nulls = (int(v) for v in tot.cpu().tolist())
-    special = np.zeros(3, np.int64)
-    if rank == 0:
-        special[1 if null_as_group else 2] = tot_nulls
-    zero = np.zeros(1, np.int64)
-    N.check(N.lib.dq_freq_add_records_device(
-        owned.handle, None, None, 1, zero.ctypes.data, zero.ctypes.data, tot_rows - n_recv,
-        special.ctypes.data, 1 if null_as_group else 0, stream))
-    return owned
+    return raw_key_count(recv, n_recv, column, dtype, data_shard.device_index(), rank, world,
+                         tot_rows, tot_nulls, null_as_group)
 
 
 def compute_frequencies_distributed(data_shard, grouping_columns, null_as_group: bool = False):
