@@ -200,6 +200,8 @@ def _load() -> ctypes.CDLL:
         "dq_format_values": (c_int, [c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
         "dq_cast_utf8": (c_int, [POINTER(dq_column), c_int, c_void_p, c_void_p, POINTER(c_int64), c_void_p]),
         "dq_cast_parse_utf8": (c_int, [c_char_p, c_int32, c_int, POINTER(c_int64), POINTER(c_double)]),
+        "dq_parse_double_utf8": (c_int, [c_char_p, c_int32, POINTER(c_double)]),
+        "dq_parse_double_fallbacks": (c_int64, []),
         "dq_schema_evaluate": (c_int, [POINTER(dq_schema_column), c_int, POINTER(dq_column), c_int,
                                        c_int64, c_void_p, c_void_p, POINTER(c_int64),
                                        POINTER(c_int64), POINTER(c_int64), c_void_p]),
@@ -264,6 +266,7 @@ EXPORTED = [
     "dq_freq_add_records_device", "dq_key_partition",
     "dq_schema_evaluate", "dq_select_plan", "dq_gather_column",
     "dq_dict_decode", "dq_freq_add_dict_device", "dq_split_rows",
+    "dq_parse_double_utf8", "dq_parse_double_fallbacks",
 ]
 FREQ_RECORD_BYTES = 24  # sizeof(dq_freq_record)
 
@@ -323,6 +326,18 @@ def cast_parse_utf8(text: bytes, to_type: int) -> tuple:
     lv, dv = c_int64(0), c_double(0.0)
     res = lib.dq_cast_parse_utf8(text, len(text), to_type, ctypes.byref(lv), ctypes.byref(dv))
     return res, (None if res != 1 else lv.value if to_type == INT64 else dv.value)
+
+
+def parse_double_utf8(text: bytes):
+    """java.lang.Double.parseDouble(text) -- the double, or None for NumberFormatException -- from
+    the complete parser the device code uses (parse_double.h), run on the host."""
+    dv = c_double(0.0)
+    return dv.value if lib.dq_parse_double_utf8(text, len(text), ctypes.byref(dv)) else None
+
+
+def parse_double_fallbacks() -> int:
+    """How many parse_double_utf8 calls so far needed the parser's exact multi-word fallback."""
+    return int(lib.dq_parse_double_fallbacks())
 
 
 def release_cached_memory() -> None:

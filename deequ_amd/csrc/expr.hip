@@ -7,6 +7,7 @@
 #include "device_util.h"
 #include "kernels.h"
 #include "jfmt.h"
+#include "parse_double.h"
 
 namespace dq {
 
@@ -52,100 +53,16 @@ DQ_DEV int cmp_vals(const V& a, const V& b) {
   return cmp3_i64(a.i, b.i);
 }
 
-// Java Double.parseDouble subset (what Spark 2.2's Cast(StringType -> DoubleType) calls): trims
-// ASCII whitespace/control chars, sign, digits, '.', exponent, optional [dDfF] suffix, NaN,
-// Infinity.  Correctly rounded when the decimal significand < 2^53 and |exp10| <= 22; otherwise the
-// nearest of two roundings (documented).  Returns false when the string is not a number -> NULL.
+// java.lang.Double.parseDouble (what Spark 2.2's Cast(StringType -> DoubleType) calls, and with it
+// every `string <op> number` comparison through PromoteStrings): the complete parser of
+// parse_double.h -- every form of Double.valueOf's grammar (decimal with exponent and suffix, NaN,
+// Infinity, hex), correctly rounded, the exact multi-word fallback included.  Returns false where
+// Java throws NumberFormatException -> NULL.  The parser reads s[0, len) with plain byte loads;
+// DevBytes::u8(k) returns that same byte (it exists so that wider loads stay inside the
+// allocation), so the two are equivalent here.
 DQ_DEV bool parse_f64(const uint8_t* s, int32_t len, double& out) {
-  DevBytes rd{s};
-  int32_t b = 0, e = len;
-  while (b < e && rd.u8(b) <= 32) ++b;
-  while (e > b && rd.u8(e - 1) <= 32) --e;
-  if (b >= e) return false;
-  bool neg = false;
-  uint32_t c = rd.u8(b);
-  if (c == '+' || c == '-') {
-    neg = c == '-';
-    ++b;
-  }
-  if (e - b == 3 && rd.u8(b) == 'N' && rd.u8(b + 1) == 'a' && rd.u8(b + 2) == 'N') {
-    out = __builtin_nan("");
-    return true;
-  }
-  if (e - b == 8) {
-    const char* inf = "Infinity";
-    bool ok = true;
-    for (int k = 0; k < 8; ++k) ok &= rd.u8(b + k) == (uint32_t)inf[k];
-    if (ok) {
-      out = neg ? -__builtin_inf() : __builtin_inf();
-      return true;
-    }
-  }
-  if (e > b) {
-    uint32_t last = rd.u8(e - 1);
-    if (last == 'd' || last == 'D' || last == 'f' || last == 'F') --e;
-  }
-  uint64_t mant = 0;
-  int digits = 0, exp10 = 0;
-  bool any = false, dot = false, overflow_digits = false;
-  int32_t k = b;
-  for (; k < e; ++k) {
-    c = rd.u8(k);
-    if (c >= '0' && c <= '9') {
-      any = true;
-      if (mant < 100000000000000000ULL) {
-        mant = mant * 10 + (c - '0');
-        if (mant) ++digits;
-        if (dot) --exp10;
-      } else {
-        overflow_digits = true;
-        if (!dot) ++exp10;
-      }
-    } else if (c == '.' && !dot) {
-      dot = true;
-    } else {
-      break;
-    }
-  }
-  if (!any) return false;
-  if (k < e) {
-    c = rd.u8(k);
-    if (c != 'e' && c != 'E') return false;
-    ++k;
-    bool eneg = false;
-    if (k < e && (rd.u8(k) == '+' || rd.u8(k) == '-')) {
-      eneg = rd.u8(k) == '-';
-      ++k;
-    }
-    if (k >= e) return false;
-    int ev = 0;
-    for (; k < e; ++k) {
-      c = rd.u8(k);
-      if (c < '0' || c > '9') return false;
-      if (ev < 100000) ev = ev * 10 + (c - '0');
-    }
-    exp10 += eneg ? -ev : ev;
-  }
-  (void)overflow_digits;
-  (void)digits;
-  double v = (double)mant;
-  const double p10[23] = {1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,  1e8,  1e9,  1e10, 1e11,
-                          1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
-  if (exp10 >= 0) {
-    while (exp10 > 22) {
-      v *= 1e22;
-      exp10 -= 22;
-    }
-    v *= p10[exp10];
-  } else {
-    while (exp10 < -22) {
-      v /= 1e22;
-      exp10 += 22;
-    }
-    v /= p10[-exp10];
-  }
-  out = neg ? -v : v;
-  return true;
+  int flags;
+  return castp::parse_double(s, len, out, flags);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -243,8 +243,9 @@ def _cast_column(data, name: str, to_type: int):
                                    validity.data_ptr(), ctypes.byref(bad), stream))
         if bad.value:
             raise NotImplementedError(
-                f"cast of column {name} to double: {bad.value} value(s) need parseDouble forms "
-                "(exponent / NaN / Infinity / > 19 significant digits) this build does not convert")
+                f"cast of column {name} to double: {bad.value} value(s) are in a non-plain "
+                "parseDouble form (exponent / NaN / Infinity / hex / f-d suffix) that the cast "
+                "reports and does not convert")
         nb = dict(b)
         nb[name] = ColumnBatch(to_type, c.length, validity, values, None, 0)
         batches.append(nb)

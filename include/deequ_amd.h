@@ -566,19 +566,19 @@ int64_t dq_cached_device_bytes(int device);
  * ColumnProfiler's cast of string columns inferred numeric (profiles/ColumnProfiler.scala:311-320,
  * 389-405).  to_type DQ_INT64 follows UTF8String.toLong (sign, digits, '.' + digits truncated);
  * DQ_FLOAT64 follows java.lang.Double.parseDouble.  Every row has one of three results:
- *   value        the converted number (validity bit 1).  For DQ_FLOAT64 at least every plain
- *                decimal (bytes <= ' ' trimmed, optional sign, digits with at most one '.', no
- *                exponent or suffix) whose digits without leading and trailing zeros are d <= 2^53
- *                and whose matching power of ten e has |e| <= 22, or e > 22 with
- *                d * 10^(e - 22) <= 2^53; zero in any spelling.  The result is the double nearest
- *                to the decimal, the sign of zero kept.
+ *   value        the converted number (validity bit 1).  For DQ_FLOAT64 every plain decimal (bytes
+ *                <= ' ' trimmed, optional sign, digits with at most one '.', no exponent or
+ *                suffix) of any length and magnitude.  The result is the double nearest to the
+ *                decimal, ties to even: +-Infinity above the double range, +-0.0 below it, the sign
+ *                of zero kept.
  *   NULL         Spark's NULL (validity bit 0): toLong returns false / parseDouble throws
  *                NumberFormatException, decided by the grammar of Double.valueOf's documentation
  *                ("1e", "d", "0x1", "1d2" are NULL like "abc").  A NULL input row stays NULL.
- *   unsupported  DQ_FLOAT64 only: parseDouble reads the string but it is not converted here (an
- *                exponent, NaN / Infinity, a hex form, an f/F/d/D suffix, a plain decimal outside
- *                the window above).  The row is NULL and counted in *n_unsupported; the caller must
- *                treat a non-zero count as a failure.
+ *   unsupported  DQ_FLOAT64 only: a non-plain form parseDouble reads (an exponent, NaN / Infinity,
+ *                a hex form, an f/F/d/D suffix).  The profiler never sends one (DataType infers
+ *                Fractional for plain decimals only), so the cast reports it rather than convert
+ *                it: the row is NULL and counted in *n_unsupported; the caller must treat a
+ *                non-zero count as a failure.
  * validity_out holds (length + 7) / 8 bytes, LSB-first, the bits past the last row zero; values_out
  * holds length int64 / double, 0 wherever the validity bit is 0.  Synchronises `hip_stream`. */
 dq_status dq_cast_utf8(const dq_column* in, int to_type, void* values_out, uint8_t* validity_out,
@@ -588,6 +588,14 @@ dq_status dq_cast_utf8(const dq_column* in, int to_type, void* values_out, uint8
  * 2 = unsupported.  The output that is written holds 0 unless the result is 1. */
 int dq_cast_parse_utf8(const uint8_t* s, int32_t n, int to_type, int64_t* long_out,
                        double* double_out);
+/* java.lang.Double.parseDouble of one string of n bytes, computed on the host by the parser the
+ * device code uses (csrc/parse_double.h), every form included (exponent, suffix, NaN, Infinity,
+ * hex): 1 and the correctly rounded double in *out, or 0 (and 0.0) for NumberFormatException.
+ * dq_parse_double_fallbacks: how many calls since the library was loaded needed the exact
+ * multi-word comparison, the last of the parser's three steps (tests use it to see that their
+ * inputs exercise both the fast steps and the fallback). */
+int dq_parse_double_utf8(const uint8_t* s, int32_t n, double* out);
+int64_t dq_parse_double_fallbacks(void);
 
 /* ------------------------------------------------------------------------------------------------
  * Row-level schema validation (schema/RowLevelSchemaValidator.scala:183-281) and the row selection
