@@ -63,10 +63,12 @@ def type_name(t: int) -> str:
 # dq_xop
 (X_COL, X_NULL, X_BOOL, X_I64, X_F64, X_STR, X_IS_NULL, X_IS_NOT_NULL, X_NOT, X_AND, X_OR, X_EQ,
  X_NE, X_LT, X_LE, X_GT, X_GE, X_EQ_NULL_SAFE, X_IN, X_CAST_F64, X_REGEX, X_CAST_F32,
- X_DEC128, X_LIKE, X_ARITH, X_FUNC) = range(1, 27)
+ X_DEC128, X_LIKE, X_ARITH, X_FUNC, X_CAST_STR, X_DATE, X_TIMESTAMP) = range(1, 30)
 # dq_arith_op / dq_func (the `which` word of X_ARITH / X_FUNC)
 AR_ADD, AR_SUB, AR_MUL, AR_DIV, AR_MOD, AR_NEG = range(1, 7)
 FN_ABS, FN_LENGTH, FN_COALESCE, FN_ISNAN = range(1, 5)
+(FN_YEAR, FN_MONTH, FN_DAYOFMONTH, FN_TO_DATE, FN_DATEDIFF, FN_DATE_ADD,
+ FN_DATE_SUB) = range(16, 23)   # the date functions
 
 # dq_index_type (the integers of a dictionary column's indices)
 (INDEX_INT8, INDEX_UINT8, INDEX_INT16, INDEX_UINT16, INDEX_INT32, INDEX_UINT32, INDEX_INT64,

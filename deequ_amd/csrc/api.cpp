@@ -106,6 +106,7 @@ struct Node {
   int op = 0;
   int col = -1;
   int rt = 0;  // DQ_X_ARITH / DQ_X_FUNC: the result's dq_type (i = which)
+  int slot = 0;  // DQ_X_CAST_STR: the text slot it prints into (assign_text_slots)
   int64_t i = 0;
   double d = 0.0;
   std::string s;
@@ -132,8 +133,11 @@ static bool parse_node(const int64_t* w, int n, int& pos, std::unique_ptr<Node>&
     case DQ_X_NULL: break;
     case DQ_X_BOOL:
     case DQ_X_I64:
+    case DQ_X_DATE:
+    case DQ_X_TIMESTAMP:
       if (pos >= n) return false;
       node->i = w[pos++];
+      if (node->op == DQ_X_DATE && (node->i < INT32_MIN || node->i > INT32_MAX)) return false;
       break;
     case DQ_X_F64:
       if (pos >= n) return false;
@@ -158,6 +162,7 @@ static bool parse_node(const int64_t* w, int n, int& pos, std::unique_ptr<Node>&
     case DQ_X_NOT:
     case DQ_X_CAST_F64:
     case DQ_X_CAST_F32:
+    case DQ_X_CAST_STR:
       if (!child()) return false;
       break;
     case DQ_X_AND:
@@ -253,6 +258,13 @@ static bool parse_node(const int64_t* w, int n, int& pos, std::unique_ptr<Node>&
         case DQ_FN_LENGTH: ok = na == 1 && rt == DQ_INT32; break;
         case DQ_FN_COALESCE: ok = na >= 2 && na <= 8 && ((rt >= DQ_INT8 && rt <= DQ_FLOAT64) || rt == DQ_UTF8); break;
         case DQ_FN_ISNAN: ok = na == 1 && rt == DQ_BOOL; break;
+        case DQ_FN_YEAR:
+        case DQ_FN_MONTH:
+        case DQ_FN_DAYOFMONTH: ok = na == 1 && rt == DQ_INT32; break;
+        case DQ_FN_TO_DATE: ok = na == 1 && rt == DQ_DATE32; break;
+        case DQ_FN_DATEDIFF: ok = na == 2 && rt == DQ_INT32; break;
+        case DQ_FN_DATE_ADD:
+        case DQ_FN_DATE_SUB: ok = na == 2 && rt == DQ_DATE32; break;
         default: break;
       }
       if (!ok) return false;
@@ -268,10 +280,13 @@ static bool parse_node(const int64_t* w, int n, int& pos, std::unique_ptr<Node>&
   return true;
 }
 
-// The operators only the generic interpreter evaluates (LIKE, arithmetic, scalar functions): an
-// expression that holds one anywhere is materialised as an expression bitmap, never fused.
+// The operators only the generic interpreter evaluates (LIKE, arithmetic, scalar and date functions,
+// the cast to string, date / timestamp literals): an expression that holds one anywhere is
+// materialised as an expression bitmap, never fused.
 static bool interpreter_only(const Node& n) {
-  if (n.op == DQ_X_LIKE || n.op == DQ_X_ARITH || n.op == DQ_X_FUNC) return true;
+  if (n.op == DQ_X_LIKE || n.op == DQ_X_ARITH || n.op == DQ_X_FUNC || n.op == DQ_X_CAST_STR ||
+      n.op == DQ_X_DATE || n.op == DQ_X_TIMESTAMP)
+    return true;
   for (auto& k : n.kids)
     if (interpreter_only(*k)) return true;
   return false;
@@ -341,6 +356,9 @@ static void compile_postfix(const Node& n, std::vector<XInstr>& prog, std::strin
     case DQ_X_IN: ins = {XI_IN, (int32_t)n.kids.size() - 1, 0}; break;
     case DQ_X_CAST_F64: ins = {XI_CAST_F64, 0, 0}; break;
     case DQ_X_CAST_F32: ins = {XI_CAST_F64, 1, 0}; break;  // a = 1: round to float
+    case DQ_X_CAST_STR: ins = {XI_CAST_STR, n.slot < kTextSlots ? n.slot : 0, 0}; break;
+    case DQ_X_DATE: ins = {XI_DATE, 0, n.i}; break;
+    case DQ_X_TIMESTAMP: ins = {XI_TIMESTAMP, 0, n.i}; break;
     case DQ_X_REGEX: {
       while (pool.size() % 8) pool.push_back('\0');
       ins = {XI_REGEX, (int32_t)n.i, (int64_t)pool.size()};
@@ -373,32 +391,138 @@ static bool casts_string_to_float(const Node& n, const std::vector<int32_t>& typ
   return false;
 }
 
-// Where a decimal / date / timestamp column may appear in an expression (deequ_amd.h, DQ_X_DEC128):
-// the interpreter has no other arithmetic for them, so anything else is refused, never evaluated
-// in the wrong domain.  Returns false and names the offending use in `why`.
+// What kind of value a node is, as far as the typed-use rules below need it.
+enum ValKind { VK_NULL, VK_BOOL, VK_NUM, VK_STR, VK_DEC, VK_DATE, VK_TS };
+
+static ValKind kind_of(const Node& n, const std::vector<int32_t>& types) {
+  switch (n.op) {
+    case DQ_X_COL: {
+      const int t = types[n.col];
+      if (t == DQ_DATE32) return VK_DATE;
+      if (t == DQ_TIMESTAMP_US) return VK_TS;
+      if (is_decimal(t)) return VK_DEC;
+      return t == DQ_UTF8 ? VK_STR : (t == DQ_BOOL ? VK_BOOL : VK_NUM);
+    }
+    case DQ_X_NULL: return VK_NULL;
+    case DQ_X_I64:
+    case DQ_X_F64:
+    case DQ_X_CAST_F64:
+    case DQ_X_CAST_F32:
+    case DQ_X_ARITH: return VK_NUM;
+    case DQ_X_STR:
+    case DQ_X_CAST_STR: return VK_STR;
+    case DQ_X_DEC128: return VK_DEC;
+    case DQ_X_DATE: return VK_DATE;
+    case DQ_X_TIMESTAMP: return VK_TS;
+    case DQ_X_FUNC:
+      return n.rt == DQ_DATE32 ? VK_DATE : (n.rt == DQ_UTF8 ? VK_STR : (n.rt == DQ_BOOL ? VK_BOOL : VK_NUM));
+    default: return VK_BOOL;
+  }
+}
+
+static bool is_date_func(const Node& n) { return n.op == DQ_X_FUNC && n.i >= DQ_FN_YEAR; }
+
+// Gives every DQ_X_CAST_STR its text slot.  `live`: the slots holding a printed value that a later
+// instruction still reads, in evaluation order; `peak`: the most there were.  A cast of a
+// non-string value prints into the first free slot.  A printed value lives until the operator above
+// it has run, unless that operator hands the text on unchanged: a string coalesce returns one of
+// its arguments, and a cast of a string operand returns the operand, so whatever slots their
+// operands hold stay live through them (the text may sit in any of those).
+static void assign_text_slots(Node& n, const std::vector<int32_t>& types, int& live, int& peak) {
+  const int base = live;
+  for (auto& k : n.kids) assign_text_slots(*k, types, live, peak);
+  if (n.op == DQ_X_CAST_STR) {
+    if (kind_of(*n.kids[0], types) != VK_STR) {  // prints: nothing below it is read again
+      n.slot = base;
+      live = base + 1;
+    }
+  } else if (!(n.op == DQ_X_FUNC && n.i == DQ_FN_COALESCE && n.rt == DQ_UTF8)) {
+    live = base;
+  }
+  peak = std::max(peak, live);
+}
+
+// Does the expression hold an operation only the text-capable interpreter runs (kernels.h
+// launch_expr): a cast to string, a date / timestamp literal, a date function, or a comparison /
+// IN over date / timestamp values?
+static bool needs_text_kernel(const Node& n, const std::vector<int32_t>& types) {
+  if (n.op == DQ_X_CAST_STR || n.op == DQ_X_DATE || n.op == DQ_X_TIMESTAMP || is_date_func(n)) return true;
+  if ((n.op >= DQ_X_EQ && n.op <= DQ_X_EQ_NULL_SAFE) || n.op == DQ_X_IN) {
+    // (typed_uses_ok pairs such a value with its own kind or NULL only; every operand is looked
+    // at all the same, so that no tag 6 / 7 comparison can reach expr_kernel, where it is NULL)
+    for (auto& k : n.kids) {
+      const ValKind vk = kind_of(*k, types);
+      if (vk == VK_DATE || vk == VK_TS) return true;
+    }
+  }
+  for (auto& k : n.kids)
+    if (needs_text_kernel(*k, types)) return true;
+  return false;
+}
+
+// Where a decimal / date / timestamp value may appear in an expression (deequ_amd.h, DQ_X_DEC128
+// and DQ_X_TIMESTAMP): the interpreter has no other arithmetic for them, so anything else is
+// refused, never evaluated in the wrong domain.  Returns false and names the offending use in `why`.
 static bool typed_uses_ok(const Node& n, const std::vector<int32_t>& types, std::string& why) {
   auto dec_col = [&](const Node* x) { return x->op == DQ_X_COL && is_decimal(types[x->col]); };
   auto special = [&](const Node* x) {
     return x->op == DQ_X_COL && (is_decimal(types[x->col]) || is_temporal(types[x->col]));
   };
+  auto temporal = [](ValKind k) { return k == VK_DATE || k == VK_TS; };
+  // the operands of a use that admits date / timestamp values: such a column stands as it is,
+  // anything else is checked in turn
+  auto operands_ok = [&](size_t from) {
+    for (size_t k = from; k < n.kids.size(); ++k) {
+      const Node& x = *n.kids[k];
+      if (x.op == DQ_X_COL && is_temporal(types[x.col])) continue;
+      if (x.op == DQ_X_DATE || x.op == DQ_X_TIMESTAMP) continue;
+      if (!typed_uses_ok(x, types, why)) return false;
+    }
+    return true;
+  };
   switch (n.op) {
     case DQ_X_COL:
       if (special(&n)) {
         why = "a decimal / date / timestamp column used outside IS [NOT] NULL, a comparison with a "
-              "decimal literal, CAST AS DOUBLE or a regex";
+              "value of its own type, CAST AS DOUBLE (decimal), CAST AS STRING, a date function or "
+              "a regex";
         return false;
       }
       return true;
     case DQ_X_DEC128:
       why = "a decimal literal outside a comparison with a decimal column";
       return false;
+    case DQ_X_DATE:
+    case DQ_X_TIMESTAMP:
+      why = "a date / timestamp literal outside a comparison with a value of its own type, CAST AS "
+            "STRING, a date function or a regex";
+      return false;
     case DQ_X_IS_NULL:
     case DQ_X_IS_NOT_NULL:
     case DQ_X_REGEX:
+    case DQ_X_CAST_STR:
       if (special(n.kids[0].get())) return true;
+      if (temporal(kind_of(*n.kids[0], types))) return operands_ok(0);
       break;
     case DQ_X_CAST_F64:
       if (dec_col(n.kids[0].get())) return true;
+      break;
+    case DQ_X_FUNC:
+      if (is_date_func(n)) {
+        const bool two = n.kids.size() == 2;
+        const bool day_count = n.i == DQ_FN_DATE_ADD || n.i == DQ_FN_DATE_SUB;
+        for (size_t k = 0; k < n.kids.size(); ++k) {
+          const ValKind vk = kind_of(*n.kids[k], types);
+          const bool ok = two && k == 1 && day_count ? (vk == VK_NUM || vk == VK_NULL)
+                                                     : (temporal(vk) || vk == VK_NULL);
+          if (!ok) {
+            why = "a date function over an argument that is no date / timestamp (or, for the "
+                  "number of days, no integral value)";
+            return false;
+          }
+        }
+        return operands_ok(0);
+      }
       break;
     case DQ_X_IN:
       if (dec_col(n.kids[0].get())) {
@@ -409,6 +533,20 @@ static bool typed_uses_ok(const Node& n, const std::vector<int32_t>& types, std:
           }
         return true;
       }
+      {
+        bool any = false, same = true;
+        const ValKind kx = kind_of(*n.kids[0], types);
+        for (auto& k : n.kids) {
+          const ValKind vk = kind_of(*k, types);
+          any = any || temporal(vk);
+          same = same && (vk == kx || vk == VK_NULL);
+        }
+        if (any && !(temporal(kx) && same)) {
+          why = "a date / timestamp value IN a list with items of another type";
+          return false;
+        }
+        if (any) return operands_ok(0);
+      }
       break;
     default:
       if (is_cmp(n.op) || n.op == DQ_X_EQ_NULL_SAFE) {
@@ -416,6 +554,14 @@ static bool typed_uses_ok(const Node& n, const std::vector<int32_t>& types, std:
         const Node* b = n.kids[1].get();
         if (dec_col(a) && (b->op == DQ_X_DEC128 || b->op == DQ_X_NULL)) return true;
         if (dec_col(b) && (a->op == DQ_X_DEC128 || a->op == DQ_X_NULL)) return true;
+        const ValKind ka = kind_of(*a, types), kb = kind_of(*b, types);
+        if (temporal(ka) || temporal(kb)) {
+          if (ka != kb && ka != VK_NULL && kb != VK_NULL) {
+            why = "a date / timestamp value compared with a value of another type";
+            return false;
+          }
+          return operands_ok(0);
+        }
       }
       break;
   }
@@ -586,6 +732,8 @@ struct TaskPlan {
 
 struct MatExpr {
   int expr = -1;                // index in desc exprs
+  bool text = false;            // runs in the text-capable interpreter (needs_text_kernel)
+  int text_slots = 0;           // the text slots its casts to string use (compile_postfix)
   std::vector<XInstr> prog;
   std::string pool;
 };
@@ -593,6 +741,7 @@ struct MatExpr {
 struct dq_plan {
   std::vector<int32_t> types;
   std::vector<std::unique_ptr<Node>> exprs;
+  std::vector<int> text_slots;  // per expression: the text slots its casts to string use
   std::vector<dq_agg> aggs;
   std::vector<Slot> slots;
   std::vector<TaskPlan> tasks;
@@ -630,6 +779,8 @@ static int mat_index(dq_plan* p, int expr) {
   MatExpr m;
   m.expr = expr;
   compile_postfix(*p->exprs[expr], m.prog, m.pool);
+  m.text = needs_text_kernel(*p->exprs[expr], p->types);
+  m.text_slots = p->text_slots[expr];
   int idx = (int)p->mat.size();
   p->mat.push_back(std::move(m));
   p->mat_of[expr] = idx;
@@ -673,6 +824,13 @@ extern "C" dq_status dq_plan_create(const dq_plan_desc* desc, dq_plan** out) {
     // (only the interpreter has a stack: a long list that fuses into a TK_STR_IN task never
     // reaches it, so the depth is checked where an expression is materialised)
     too_deep.push_back(stack_depth(*n) > kMaxStack);
+    int live = 0, peak = 0;
+    assign_text_slots(*n, p->types, live, peak);
+    if (peak > kTextSlots)
+      return fail(DQ_ERR_UNSUPPORTED,
+                  "expression %d holds %d values cast to string at once; the interpreter has %d text "
+                  "slots", e, peak, kTextSlots);
+    p->text_slots.push_back(peak);
     if (casts_string_to_float(*n, p->types))
       return fail(DQ_ERR_UNSUPPORTED, "expression %d casts a string to FLOAT", e);
     std::string why;
@@ -895,8 +1053,11 @@ extern "C" dq_status dq_plan_explain(const dq_plan* plan, char* buf, size_t buf_
   std::string s;
   char line[256];
   for (size_t k = 0; k < plan->mat.size(); ++k) {
-    snprintf(line, sizeof(line), "expr[%zu] = bitmap of expression %d (%zu instructions)\n", k,
-             plan->mat[k].expr, plan->mat[k].prog.size());
+    char text[48] = "";
+    if (plan->mat[k].text)
+      snprintf(text, sizeof(text), ", text interpreter: %d text slots", plan->mat[k].text_slots);
+    snprintf(line, sizeof(line), "expr[%zu] = bitmap of expression %d (%zu instructions%s)\n", k,
+             plan->mat[k].expr, plan->mat[k].prog.size(), text);
     s += line;
   }
   for (const TaskPlan& t : plan->tasks) {
@@ -1489,7 +1650,7 @@ extern "C" dq_status dq_scan_device_batches(const dq_plan* plan, const dq_column
                                val, vld, stream));
         } else {
           HIP_TRY(launch_expr(s->d_prog.p + s->prog_off[k], (int)plan->mat[k].prog.size(),
-                              s->d_cols[slot].p + (size_t)b * ncol, s->d_pool.p, rows[b], val, vld,
+                              plan->mat[k].text, s->d_cols[slot].p + (size_t)b * ncol, s->d_pool.p, rows[b], val, vld,
                               stream));
         }
       }

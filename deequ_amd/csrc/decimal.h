@@ -329,6 +329,22 @@ DQ_HD int ts_format(int64_t micros, char* out) {
   return n;
 }
 
+// Cast(TimestampType -> DateType) in UTC: the day that holds the instant, floored (an instant
+// before the epoch belongs to the earlier day; DateTimeUtils.millisToDays)
+DQ_HD int64_t ts_to_days(int64_t micros) {
+  const int64_t per_day = 86400000000LL;
+  return micros / per_day - (micros % per_day < 0 ? 1 : 0);
+}
+
+// DateTimeUtils.getYear / getMonth / getDayOfMonth of a day count (proleptic Gregorian);
+// which: 0 year, 1 month, 2 day of month
+DQ_HD int32_t date_field(int64_t days, int which) {
+  int64_t y;
+  int m, d;
+  civil_from_days(days, y, m, d);
+  return which == 0 ? (int32_t)y : (which == 1 ? m : d);
+}
+
 // XxHash64Function.hash of a Decimal of precision p (StatefulHyperloglogPlus.scala:91)
 DQ_HD uint64_t dec_hash(uint64_t lo, int64_t hi, int precision, uint64_t seed) {
   if (precision <= 18) return xxh_long(lo, seed);

@@ -35,8 +35,14 @@ DQ_DEV int cmp_str(const uint8_t* a, int32_t la, const uint8_t* b, int32_t lb) {
   return la == lb ? 0 : (la < lb ? -1 : 1);
 }
 
-// three-way compare of two non-NULL values; returns 2 when incomparable
+// three-way compare of two non-NULL values; returns 2 when incomparable.  kText: the interpreter
+// instantiation that also compares dates (int days) and timestamps (int64 microseconds) with
+// their own kind (dq_plan_create admits no other pairing: the host casts one side to string)
+template <bool kText>
 DQ_DEV int cmp_vals(const V& a, const V& b) {
+  if constexpr (kText) {
+    if (a.tag >= 6 || b.tag >= 6) return a.tag == b.tag ? cmp3_i64(a.i, b.i) : 2;
+  }
   if (a.tag == 5 && b.tag == 5) {  // unscaled at one scale (the plan aligns a literal's scale)
     const int64_t ah = __builtin_bit_cast(int64_t, a.d), bh = __builtin_bit_cast(int64_t, b.d);
     if (ah != bh) return ah < bh ? -1 : 1;
@@ -265,11 +271,72 @@ DQ_DEV bool like_match(const uint8_t* s, int32_t n, const uint8_t* program, int3
   }
 }
 
-__global__ void __launch_bounds__(kBlock) expr_kernel(const XInstr* __restrict__ prog, int n_instr,
-                                                      const DevCol* __restrict__ cols,
-                                                      const uint8_t* __restrict__ pool, int64_t rows,
-                                                      uint64_t* __restrict__ out_val,
-                                                      uint64_t* __restrict__ out_vld) {
+// Spark's Cast(x AS STRING) of a non-NULL, non-string value into buf (kFmtMax bytes hold every
+// form: decimal.h); returns the length.  What XI_REGEX prints inline, for XI_CAST_STR.
+DQ_DEV int32_t value_text(const V& a, char* buf) {
+  if (a.tag == 5) return dec_format((uint64_t)a.i, __builtin_bit_cast(int64_t, a.d), a.len, buf);
+  if (a.tag == 6) return date_format(a.i, buf);
+  if (a.tag == 7) return ts_format(a.i, buf);
+  if (a.tag == 3) return a.len ? jfmt::float_to_java((float)a.d, buf) : jfmt::double_to_java(a.d, buf);
+  int nb = 0;
+  if (a.tag == 1) {
+    const char* t = a.i ? "true" : "false";
+    for (; t[nb]; ++nb) buf[nb] = t[nb];
+    return nb;
+  }
+  uint64_t m = a.i < 0 ? 0ULL - (uint64_t)a.i : (uint64_t)a.i;
+  char tmp[20];
+  int nd = 0;
+  do {
+    tmp[nd++] = (char)('0' + m % 10);
+    m /= 10;
+  } while (m);
+  if (a.i < 0) buf[nb++] = '-';
+  while (nd) buf[nb++] = tmp[--nd];
+  return nb;
+}
+
+// The day count a date function reads: a date's own, a timestamp's day in UTC; false otherwise
+// (NULL included)
+DQ_DEV bool date_arg(const V& a, int64_t& days) {
+  if (a.tag == 6) days = a.i;
+  else if (a.tag == 7) days = ts_to_days(a.i);
+  else return false;
+  return true;
+}
+
+// The date functions of DQ_X_FUNC over the top of the stack (two-argument ones: a = the first
+// argument, b = the second); NULL on a NULL argument
+DQ_DEV V date_func(int which, const V& a, const V& b) {
+  int64_t x, y;
+  if (!date_arg(a, x)) return kNullV;
+  switch (which) {
+    case DQ_FN_YEAR: return V{2, 0, date_field(x, 0), 0.0, nullptr};
+    case DQ_FN_MONTH: return V{2, 0, date_field(x, 1), 0.0, nullptr};
+    case DQ_FN_DAYOFMONTH: return V{2, 0, date_field(x, 2), 0.0, nullptr};
+    case DQ_FN_TO_DATE: return V{6, 0, x, 0.0, nullptr};
+    case DQ_FN_DATEDIFF:
+      if (!date_arg(b, y)) return kNullV;
+      return V{2, 0, (int32_t)((uint64_t)x - (uint64_t)y), 0.0, nullptr};
+    case DQ_FN_DATE_ADD:
+    case DQ_FN_DATE_SUB: {  // Int addition: wraps at 32 bits
+      if (b.tag != 2) return kNullV;
+      const uint64_t n = (uint64_t)b.i;
+      return V{6, 0, (int32_t)(which == DQ_FN_DATE_ADD ? (uint64_t)x + n : (uint64_t)x - n), 0.0, nullptr};
+    }
+    default: return kNullV;
+  }
+}
+
+// The interpreter.  kText = false is the program set of every plan without a date / timestamp
+// value or a cast to string; kText = true adds XI_CAST_STR, XI_DATE, XI_TIMESTAMP, the date
+// functions and date / timestamp comparisons, with kTextSlots per-lane text slots in private
+// memory for the printed values (kernels.h).  Two instantiations, so that the first keeps the
+// registers and scratch it had before the second existed.
+template <bool kText>
+DQ_DEV void expr_body(const XInstr* __restrict__ prog, int n_instr, const DevCol* __restrict__ cols,
+                      const uint8_t* __restrict__ pool, int64_t rows, uint64_t* __restrict__ out_val,
+                      uint64_t* __restrict__ out_vld) {
   const int lane = threadIdx.x & 63;
   const int64_t wave = ((int64_t)blockIdx.x * kBlock + threadIdx.x) >> 6;
   const int64_t n_waves = ((int64_t)gridDim.x * kBlock) >> 6;
@@ -277,6 +344,10 @@ __global__ void __launch_bounds__(kBlock) expr_kernel(const XInstr* __restrict__
   for (int64_t w = wave; w < n_words; w += n_waves) {
     const int64_t r = w * 64 + lane;
     V st[kMaxStack];
+    // printed values: dword aligned and a whole number of dwords each, so that the aligned dword
+    // loads of DevBytes (cmp_str, like_match, utf8_chars, the regex walk) stay inside a slot
+    alignas(8) char text[kText ? kTextSlots : 1][kFmtMax];
+    static_assert(kFmtMax % 8 == 0 && kFmtMax >= jfmt::kMaxChars, "a slot holds every printed value");
     int sp = 0;
     bool in_range = r < rows;
     if (in_range) {
@@ -357,12 +428,12 @@ __global__ void __launch_bounds__(kBlock) expr_kernel(const XInstr* __restrict__
             if (ins.a == DQ_X_EQ_NULL_SAFE) {
               int eq;
               if (a.tag == 0 || b.tag == 0) eq = (a.tag == 0 && b.tag == 0);
-              else eq = cmp_vals(a, b) == 0;
+              else eq = cmp_vals<kText>(a, b) == 0;
               st[sp - 1] = V{1, 0, eq, 0.0, nullptr};
             } else if (a.tag == 0 || b.tag == 0) {
               st[sp - 1] = V{0, 0, 0, 0.0, nullptr};
             } else {
-              int c = cmp_vals(a, b);
+              int c = cmp_vals<kText>(a, b);
               if (c == 2) st[sp - 1] = V{0, 0, 0, 0.0, nullptr};
               else st[sp - 1] = V{1, 0, (op_mask(ins.a) >> (c + 1)) & 1, 0.0, nullptr};
             }
@@ -379,7 +450,7 @@ __global__ void __launch_bounds__(kBlock) expr_kernel(const XInstr* __restrict__
                 const V& it = st[base + 1 + q];
                 if (it.tag == 0) {
                   saw_null = true;
-                } else if (cmp_vals(x, it) == 0) {
+                } else if (cmp_vals<kText>(x, it) == 0) {
                   found = true;
                 }
               }
@@ -477,6 +548,13 @@ __global__ void __launch_bounds__(kBlock) expr_kernel(const XInstr* __restrict__
           }
           case XI_FUNC: {  // a = dq_func | result dq_type << 8, imm = number of arguments
             const int which = ins.a & 0xff, rt = ins.a >> 8;
+            if constexpr (kText) {
+              if (which >= DQ_FN_YEAR) {
+                if (ins.imm == 2) --sp;
+                st[sp - 1] = date_func(which, st[sp - 1], st[ins.imm == 2 ? sp : sp - 1]);
+                break;
+              }
+            }
             V& a = st[sp - 1];
             if (which == DQ_FN_COALESCE) {  // the first non-NULL argument, in the common type
               const int n = (int)ins.imm;
@@ -499,10 +577,27 @@ __global__ void __launch_bounds__(kBlock) expr_kernel(const XInstr* __restrict__
             }
             break;
           }
+          case XI_CAST_STR:  // a = the text slot dq_plan_create assigned
+            if constexpr (kText) {
+              V& a = st[sp - 1];
+              if (a.tag != 0 && a.tag != 4) {
+                char* buf = text[ins.a & (kTextSlots - 1)];
+                const int32_t nb = value_text(a, buf);
+                a = V{4, nb, 0, 0.0, reinterpret_cast<const uint8_t*>(buf)};
+              }
+            }
+            break;
+          case XI_DATE:
+            if constexpr (kText) st[sp++] = V{6, 0, ins.imm, 0.0, nullptr};
+            break;
+          case XI_TIMESTAMP:
+            if constexpr (kText) st[sp++] = V{7, 0, ins.imm, 0.0, nullptr};
+            break;
           default: break;
         }
       }
     }
+    if constexpr (!kText) (void)text;
     const V& res = st[0];
     const bool valid = in_range && sp == 1 && res.tag != 0;
     const bool truth = valid && res.i != 0;
@@ -513,6 +608,22 @@ __global__ void __launch_bounds__(kBlock) expr_kernel(const XInstr* __restrict__
       out_vld[w] = bn;
     }
   }
+}
+
+__global__ void __launch_bounds__(kBlock) expr_kernel(const XInstr* __restrict__ prog, int n_instr,
+                                                      const DevCol* __restrict__ cols,
+                                                      const uint8_t* __restrict__ pool, int64_t rows,
+                                                      uint64_t* __restrict__ out_val,
+                                                      uint64_t* __restrict__ out_vld) {
+  expr_body<false>(prog, n_instr, cols, pool, rows, out_val, out_vld);
+}
+
+__global__ void __launch_bounds__(kBlock) expr_text_kernel(const XInstr* __restrict__ prog, int n_instr,
+                                                           const DevCol* __restrict__ cols,
+                                                           const uint8_t* __restrict__ pool, int64_t rows,
+                                                           uint64_t* __restrict__ out_val,
+                                                           uint64_t* __restrict__ out_vld) {
+  expr_body<true>(prog, n_instr, cols, pool, rows, out_val, out_vld);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -623,14 +734,15 @@ regex_find_kernel(const uint8_t* __restrict__ valid, const int32_t* __restrict__
 // ------------------------------------------------------------------------------------------------
 // Host-side launchers
 // ------------------------------------------------------------------------------------------------
-hipError_t launch_expr(const XInstr* prog, int n_instr, const DevCol* cols, const uint8_t* pool,
-                       int64_t rows, uint64_t* out_val, uint64_t* out_vld, hipStream_t stream) {
+hipError_t launch_expr(const XInstr* prog, int n_instr, bool text, const DevCol* cols,
+                       const uint8_t* pool, int64_t rows, uint64_t* out_val, uint64_t* out_vld,
+                       hipStream_t stream) {
   if (rows <= 0) return hipSuccess;
   int64_t words = (rows + 63) / 64;
   int64_t blocks = (words + 3) / 4;
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(expr_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, prog, n_instr,
-                     cols, pool, rows, out_val, out_vld);
+  hipLaunchKernelGGL(text ? expr_text_kernel : expr_kernel, dim3((unsigned)blocks), dim3(kBlock), 0,
+                     stream, prog, n_instr, cols, pool, rows, out_val, out_vld);
   return hipGetLastError();
 }
 

@@ -118,7 +118,11 @@ enum XiOp : int32_t {
   XI_DEC128_HI,  // ... imm = its high word (always right after XI_DEC128)
   XI_LIKE,       // a = program bytes | LikeShape << 16, imm = offset of the program in the pool
   XI_ARITH,      // a = dq_arith_op | result dq_type << 8
-  XI_FUNC        // a = dq_func | result dq_type << 8, imm = number of arguments
+  XI_FUNC,       // a = dq_func | result dq_type << 8, imm = number of arguments
+  // the text-capable instantiation's own (expr.hip expr_text_kernel)
+  XI_CAST_STR,   // a = text slot (< kTextSlots): the top of the stack as Spark's cast to string
+  XI_DATE,       // imm = days since 1970-01-01
+  XI_TIMESTAMP   // imm = microseconds since the epoch
 };
 
 // What a LIKE pattern program is, decided on the host (api.cpp like_shape) so that the shapes
@@ -140,6 +144,10 @@ struct XInstr {
 };
 
 constexpr int kMaxStack = 16;
+// Text slots of a lane in the text-capable interpreter (kFmtMax bytes each, a power of two of
+// them): the values DQ_X_CAST_STR printed that are alive at one point of a program.  Two serve a
+// date against a timestamp; dq_plan_create assigns them and refuses a program that needs more.
+constexpr int kTextSlots = 2;
 
 // Arrow bitmap at a bit offset -> bitmap at bit 0 (cast.hip; sliced Arrow arrays at the ABI).
 hipError_t launch_bitmap_rebase(const uint8_t* src, int64_t bit, int64_t rows, uint8_t* dst,
@@ -154,8 +162,10 @@ bool dict_index_type_ok(int index_type);
 hipError_t launch_dict_count(const void* indices, int index_type, const uint8_t* valid, int64_t rows,
                              int64_t entries, unsigned long long* counts, unsigned long long* words,
                              hipStream_t stream);
-hipError_t launch_expr(const XInstr* prog, int n_instr, const DevCol* cols, const uint8_t* pool,
-                       int64_t rows, uint64_t* out_val, uint64_t* out_vld, hipStream_t stream);
+// text: the program holds an operation only the text-capable instantiation runs (MatExpr::text)
+hipError_t launch_expr(const XInstr* prog, int n_instr, bool text, const DevCol* cols,
+                       const uint8_t* pool, int64_t rows, uint64_t* out_val, uint64_t* out_vld,
+                       hipStream_t stream);
 // PatternMatch over a utf8 column with a fused automaton table (expr.hip): ns * 256 u8 successors
 // then ns flag bytes (bit 0 accepted after end of text, bit 1 terminal), 16-byte aligned.
 constexpr int kRegexMaxStates = 255;

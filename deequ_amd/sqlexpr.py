@@ -11,7 +11,8 @@ Compliance.scala:47-49).  The strings Check generates are (Check.scala):
   * numeric range            ``"c IS NULL OR (c >= lo AND c <= hi)"``                :853-869
 
 This module parses that grammar (plus NOT, parentheses, <>, !=, <=>, BETWEEN, booleans, NULL,
-CAST(x AS DOUBLE / FLOAT), RLIKE, LIKE, arithmetic and six scalar functions) with Spark 2.2's
+CAST(x AS DOUBLE / FLOAT / STRING), RLIKE, LIKE, arithmetic, DATE / TIMESTAMP literals, six
+scalar and seven date functions) with Spark 2.2's
 precedence -- OR < AND < NOT < comparison / IS / IN / BETWEEN / LIKE / RLIKE < ``+ -`` <
 ``* / %`` < unary ``- +`` < primary -- and applies Spark 2.2's type coercion so the engine only
 sees typed operations:
@@ -33,7 +34,42 @@ sees typed operations:
     decimal literal: cast to double against a float / double / string operand, refused against
     an integral or decimal one (Spark does decimal arithmetic there);
   * ``abs``, ``length``, ``coalesce`` (2 to 8 arguments), ``isnan``, ``isnull``, ``isnotnull``;
-    every other function raises :class:`SqlError`.
+  * ``CAST(x AS STRING)`` of any value: Spark's text of it (``true``, decimal digits,
+    ``Double.toString`` / ``Float.toString``, ``BigDecimal.toString``, ``yyyy-MM-dd``,
+    ``yyyy-MM-dd HH:mm:ss[.f]`` in UTC), a string operand wherever one is taken -- comparisons,
+    ``IN``, ``LIKE``, ``RLIKE``, ``length``, ``coalesce``, and against a number through the string
+    -> double rule.  The implicit casts Spark inserts for ``i32 IN ('1')``, ``i32 LIKE '1%'``,
+    ``length(i32)`` and ``coalesce(s, 1)`` are still refused: the cast has to be written;
+  * date / timestamp comparisons (``PromoteStrings`` / ``findCommonTypeForBinaryComparison``):
+
+      ====================================  ====================================================
+      date vs date, timestamp vs timestamp  as int days / int64 microseconds
+      date vs string (any operator)         refused: Spark casts the date to STRING and compares
+                                            text; that cast has to be written, ``CAST(d AS
+                                            STRING) = '2020-1-1'`` (FALSE for 2020-01-01, unsigned
+                                            byte order), or the literal typed, ``DATE '...'``
+      timestamp vs string, ``< <= > >=``    the timestamp CAST AS STRING: ``ts >= '2020-01-01'``
+                                            is TRUE at midnight (the longer string sorts higher)
+      timestamp vs string, ``= <> <=>``     the STRING is cast to timestamp: a literal
+                                            ``yyyy-MM-dd`` / ``yyyy-MM-dd HH:mm:ss[.f{1,6}]`` is
+                                            folded here (UTC); any other string operand is refused
+      date vs timestamp                     both CAST AS STRING
+      date / timestamp vs number / boolean  an error (Spark 2.2: type mismatch)
+      date / timestamp vs NULL              NULL (``<=>``: FALSE / TRUE)
+      ====================================  ====================================================
+
+    ``x IN (...)`` over a date / timestamp ``x``: items of x's own type compare natively, a list
+    of strings (and NULLs) casts x to STRING (``InConversion``), any other mix is refused;
+    ``BETWEEN`` is its two comparisons;
+  * ``DATE 'yyyy-[m]m-[d]d'`` and ``TIMESTAMP 'yyyy-[m]m-[d]d hh:mm:ss[.f{1,6}]'`` literals, read as
+    ``java.sql.Date.valueOf`` / ``Timestamp.valueOf`` read them (a day up to 31 rolls into the next
+    month), in UTC, on the proleptic Gregorian calendar; what those reject, a signed field, an
+    hour above 23 / minute or second above 59, and more than 6 fractional digits raise;
+  * ``year``, ``month``, ``dayofmonth``, ``to_date``, ``datediff(end, start)``, ``date_add(x, n)``,
+    ``date_sub(x, n)`` over date or timestamp arguments (a timestamp is cast to date first: the
+    floor of micros / 86 400 000 000, UTC); ``n`` is a tinyint / smallint / int expression; a
+    string argument (Spark's lenient ``stringToDate``) is refused, ``d + 1`` too;
+  * every other function raises :class:`SqlError`.
 
 Column names resolve case-insensitively (spark.sql.caseSensitive=false).  Anything outside the
 grammar raises :class:`SqlError`, which the runner turns into a failure of the shared scan exactly
@@ -108,7 +144,10 @@ class Node:
 _KW = {"AND", "OR", "NOT", "IS", "NULL", "IN", "TRUE", "FALSE", "BETWEEN", "CAST", "AS", "RLIKE",
        "LIKE"}
 _FUNCS = {"abs": (1, 1), "length": (1, 1), "coalesce": (2, 8), "isnan": (1, 1), "isnull": (1, 1),
-          "isnotnull": (1, 1)}   # name -> (fewest, most) arguments
+          "isnotnull": (1, 1), "year": (1, 1), "month": (1, 1), "dayofmonth": (1, 1),
+          "to_date": (1, 1), "datediff": (2, 2), "date_add": (2, 2),
+          "date_sub": (2, 2)}   # name -> (fewest, most) arguments
+_DATE_FUNCS = ("year", "month", "dayofmonth", "to_date", "datediff", "date_add", "date_sub")
 
 # The engine's spelling of PatternMatch's counted expression,
 # when(regexp_extract(x, pattern, 0) != "", 1).otherwise(0) (PatternMatch.scala:44-46): TRUE when
@@ -290,6 +329,13 @@ class _Parser:
                 ty = self.take().text.upper()
                 self.expect_sym(")")
                 return Node("cast", [inner], name=ty)
+            nxt = self.peek()
+            if u in ("DATE", "TIMESTAMP") and nxt is not None and nxt.kind == "str":
+                self.i += 1
+                text = _unescape_sql_string(nxt.text)
+                if u == "DATE":
+                    return Node("lit", value=date_literal(text), ltype="date")
+                return Node("lit", value=timestamp_literal(text), ltype="ts")
             if u in _KW:
                 raise SqlError(f"unexpected keyword {t.text}")
             if self.sym("(") and t.text.lower() == FIND_NONEMPTY:
@@ -386,6 +432,78 @@ def like_program(pattern: str) -> bytes:
     return bytes(out)
 
 
+# ------------------------------------------------------------------------------------------------
+# Date and timestamp literals, folded on the host (session time zone: UTC)
+# ------------------------------------------------------------------------------------------------
+# (re.ASCII: \d is [0-9] only, as the JDK's and Spark's byte-wise readers take it)
+_DATE_RE = re.compile(r"(\d{4})-(\d{1,2})-(\d{1,2})", re.ASCII)
+_TS_RE = re.compile(r"(\d{4})-(\d{1,2})-(\d{1,2}) (\d{1,2}):(\d{1,2}):(\d{1,2})(?:\.(\d+))?", re.ASCII)
+_TS_STRING_RE = re.compile(r"(\d{4})-(\d{2})-(\d{2})(?: (\d{2}):(\d{2}):(\d{2})(?:\.(\d{1,6}))?)?", re.ASCII)
+_US_PER_DAY = 86_400_000_000
+
+
+def _days(year: int, month: int, day: int, what: str) -> int:
+    """Days since 1970-01-01 of a proleptic-Gregorian date.  java.sql.Date.valueOf checks only
+    1 <= month <= 12 and 1 <= day <= 31 and builds the date leniently: day 31 of a 30-day month is
+    the first of the next one."""
+    import datetime
+    if not (1 <= month <= 12 and 1 <= day <= 31) or year < 1:
+        raise SqlError(f"{what}: no such date")
+    try:
+        d = datetime.date(year, month, 1) + datetime.timedelta(days=day - 1)
+    except OverflowError as e:
+        raise SqlError(f"{what}: no such date") from e
+    return d.toordinal() - datetime.date(1970, 1, 1).toordinal()
+
+
+def date_literal(text: str) -> int:
+    """``DATE 'yyyy-[m]m-[d]d'`` as java.sql.Date.valueOf reads it (digits only: a sign before a
+    field, which Integer.parseInt would take, is refused), in days since the epoch."""
+    m = _DATE_RE.fullmatch(text)
+    if not m:
+        raise SqlError(f"DATE '{text}': expected yyyy-[m]m-[d]d")
+    return _days(int(m.group(1)), int(m.group(2)), int(m.group(3)), f"DATE '{text}'")
+
+
+def timestamp_literal(text: str) -> int:
+    """``TIMESTAMP 'yyyy-[m]m-[d]d hh:mm:ss[.f{1,6}]'`` as java.sql.Timestamp.valueOf reads it
+    (surrounding blanks trimmed; hours to 23, minutes and seconds to 59 -- the lenient roll-over of
+    larger ones is refused), read in UTC, in microseconds since the epoch.  More than six
+    fractional digits do not fit Spark's microseconds and are refused."""
+    what = f"TIMESTAMP '{text}'"
+    m = _TS_RE.fullmatch(text.strip(" "))
+    if not m:
+        raise SqlError(f"{what}: expected yyyy-[m]m-[d]d hh:mm:ss[.f]")
+    y, mo, d, h, mi, sec = (int(g) for g in m.groups()[:6])
+    frac = m.group(7) or ""
+    if len(frac) > 6:
+        raise SqlError(f"{what}: more than 6 fractional digits")
+    if h > 23 or mi > 59 or sec > 59:
+        raise SqlError(f"{what}: no such time of day")
+    us = int(frac.ljust(6, "0")) if frac else 0
+    return _days(y, mo, d, what) * _US_PER_DAY + ((h * 60 + mi) * 60 + sec) * 1_000_000 + us
+
+
+def timestamp_of_string(text: str) -> Optional[int]:
+    """The timestamp Spark's Cast(string AS TIMESTAMP) gives a string of the exact forms
+    ``yyyy-MM-dd`` / ``yyyy-MM-dd HH:mm:ss[.f{1,6}]`` (UTC); None for any other string, whose
+    reading by DateTimeUtils.stringToTimestamp is not restated."""
+    import datetime
+    m = _TS_STRING_RE.fullmatch(text)
+    if not m:
+        return None
+    y, mo, d = (int(g) for g in m.groups()[:3])
+    h, mi, sec = (int(g) for g in m.groups()[3:6]) if m.group(4) else (0, 0, 0)
+    try:
+        day = datetime.date(y, mo, d).toordinal() - datetime.date(1970, 1, 1).toordinal()
+    except ValueError:
+        return None
+    if h > 23 or mi > 59 or sec > 59:
+        return None
+    us = int((m.group(7) or "").ljust(6, "0") or 0)
+    return day * _US_PER_DAY + ((h * 60 + mi) * 60 + sec) * 1_000_000 + us
+
+
 def _num_literal(text: str) -> Node:
     m = re.match(r"^((?:\d+\.\d*|\.\d+|\d+)(?:[eE][+-]?\d+)?)([A-Za-z]*)$", text)
     body, suffix = m.group(1), m.group(2).upper()
@@ -467,6 +585,8 @@ class _Emitter:
                     "BIGINT": "int", "LONG": "int", "BOOLEAN": "bool"}.get(n.name, "?")
         if n.op in ("arith", "neg") or (n.op == "func" and n.name != "isnan"):
             t = self.result_type(n)
+            if t == N.DATE32:
+                return "date"
             return "str" if t == N.UTF8 else ("int" if t in N.INTEGRAL_TYPES else "float")
         return "bool"
 
@@ -494,7 +614,10 @@ class _Emitter:
                                f"which is not supported by the engine")
         elif n.op == "cast" and n.name in ("DOUBLE", "FLOAT"):
             return N.FLOAT64 if n.name == "DOUBLE" else N.FLOAT32
-        elif n.op in ("arith", "neg", "func") and self.type_of(n) != "bool":
+        elif n.op == "cast" and n.name == "STRING":
+            self.cast_str_kind(n)
+            return "str"
+        elif n.op in ("arith", "neg", "func") and self.type_of(n) not in ("bool", "date"):
             t = self.result_type(n)
             return "str" if t == N.UTF8 else t
         raise SqlError(f"{what} over a {self.type_of(n)} operand is not supported by the engine")
@@ -521,10 +644,13 @@ class _Emitter:
             t = self.promote([self.operand_type(k, f"'{n.name}'") for k in n.kids], f"'{n.name}'")
             return N.FLOAT64 if n.name == "/" else t  # the Division rule: always a double division
         what = f"{n.name}()"
+        if n.name in _DATE_FUNCS:
+            return self.date_func_type(n)
         types = [self.operand_type(k, what) for k in n.kids]
         if n.name == "length":
             if types != ["str"]:
-                raise SqlError("length() needs a string operand")
+                raise SqlError("length() needs a string operand (write CAST(x AS STRING) for the "
+                               "length of another value's text)")
             return N.INT32
         if n.name == "isnan":
             if types[0] not in (N.FLOAT32, N.FLOAT64):
@@ -534,8 +660,90 @@ class _Emitter:
             return N.UTF8
         if n.name == "coalesce" and "str" in types:
             raise SqlError("coalesce() over string and numeric arguments is not supported by the "
-                           "engine")
+                           "engine (write CAST(x AS STRING) around the numeric ones)")
         return self.promote(types, what)
+
+    # -- dates and timestamps
+    def date_func_type(self, n: Node) -> int:
+        """Checks a date function's arguments and returns its result type.  A date argument is a
+        date or a timestamp (cast to date: its UTC day); a string one, which Spark reads with the
+        lenient stringToDate, is refused."""
+        what = f"{n.name}()"
+        day_count = n.name in ("date_add", "date_sub")
+        for k in (n.kids[:1] if day_count else n.kids):
+            t = self.type_of(k)
+            if t not in ("date", "ts"):
+                raise SqlError(f"{what} needs a date or timestamp argument, not a {t} one"
+                               + (" (Spark parses the string as a date; write a DATE '...' literal)"
+                                  if t == "str" else ""))
+        if day_count:
+            t = self.type_of(n.kids[1])
+            nt = self.operand_type(n.kids[1], what) if t == "int" else None
+            if nt not in (N.INT8, N.INT16, N.INT32):
+                raise SqlError(f"{what} needs an int number of days (a tinyint, smallint or int "
+                               f"expression), as Spark's type check does")
+        return N.DATE32 if day_count or n.name == "to_date" else N.INT32
+
+    def cast_str_kind(self, n: Node) -> str:
+        t = self.type_of(n.kids[0])
+        if t not in ("str", "bool", "int", "float", "dec", "date", "ts", "null"):
+            raise SqlError(f"CAST of a {t} value AS STRING is not supported by the engine")
+        return t
+
+    def _as_string(self, n: Node) -> Node:
+        return Node("cast", [n], name="STRING")
+
+    def _emit_temporal_cmp(self, sym: str, a: Node, ta: str, b: Node, tb: str) -> None:
+        """A comparison with a date / timestamp operand, typed as Spark 2.2's PromoteStrings and
+        findCommonTypeForBinaryComparison type it."""
+        kinds = {ta, tb}
+        if ta == tb or "null" in kinds:            # days / microseconds as integers; NULL
+            pass
+        elif kinds == {"date", "ts"}:              # both sides as strings
+            a, b = self._as_string(a), self._as_string(b)
+        elif kinds == {"date", "str"}:
+            # Spark casts the DATE to string and compares text (d = '2020-1-1' is FALSE for
+            # 2020-01-01).  This implicit cast stays refused, as for i32 IN ('1'): the caller says
+            # which comparison is meant
+            raise SqlError(f"'{sym}' of a date and a string: Spark 2.2 casts the date to STRING and "
+                           f"compares text; write CAST(x AS STRING) {sym} '...' for that comparison, "
+                           f"or a DATE '...' literal to compare dates")
+        elif kinds == {"ts", "str"} and sym in ("<", "<=", ">", ">="):
+            if ta == "str":
+                b = self._as_string(b)
+            else:
+                a = self._as_string(a)
+        elif kinds == {"ts", "str"}:               # =, <>, <=>: the STRING is cast to timestamp
+            s = a if ta == "str" else b
+            us = timestamp_of_string(s.value) if s.op == "lit" else None
+            if us is None:
+                raise SqlError(f"'{sym}' of a timestamp and a string: Spark parses the string as a "
+                               f"timestamp, which the engine does only for a literal of the form "
+                               f"'yyyy-MM-dd' or 'yyyy-MM-dd HH:mm:ss[.f]' (write a TIMESTAMP '...' "
+                               f"literal)")
+            lit = Node("lit", value=us, ltype="ts")
+            a, b = (lit, b) if ta == "str" else (a, lit)
+        else:
+            other = tb if ta in ("date", "ts") else ta
+            this = ta if ta in ("date", "ts") else tb
+            raise SqlError(f"cannot compare a {this} value with a {other} one (Spark 2.2 reports a "
+                           f"type mismatch)")
+        self.words.append(_CMP[sym])
+        self.emit(a)
+        self.emit(b)
+
+    def _emit_temporal_in(self, x: Node, tx: str, items: List[Node], tis: List[str]) -> None:
+        if all(t in (tx, "null") for t in tis):    # natively
+            pass
+        elif all(t in ("str", "null") for t in tis):   # InConversion with string promotion
+            x = self._as_string(x)
+        else:
+            raise SqlError(f"a {tx} value IN a list that mixes other types is not supported by the "
+                           f"engine")
+        self.words += [N.X_IN, len(items)]
+        self.emit(x)
+        for i in items:
+            self.emit(i)
 
     def emit_operand(self, k: Node, what: str):
         """An operand of an arithmetic operator / numeric function: a string under CAST AS DOUBLE,
@@ -571,11 +779,22 @@ class _Emitter:
                 w += [N.X_I64, v]
             elif t == "float":
                 w += [N.X_F64, struct.unpack("<q", struct.pack("<d", v))[0]]
+            elif t == "date":
+                w += [N.X_DATE, v]
+            elif t == "ts":
+                w += [N.X_TIMESTAMP, v]
             elif t == "str":
                 b = v.encode("utf-8")
                 w += [N.X_STR, len(b)]
                 padded = b + b"\0" * ((-len(b)) % 8)
                 w += list(struct.unpack(f"<{len(padded) // 8}q", padded)) if padded else []
+            return
+        if n.op == "cast" and n.name == "STRING":
+            self.cast_str_kind(n)
+            if want == "float":                    # against a number: the text parsed as a double
+                w.append(N.X_CAST_F64)
+            w.append(N.X_CAST_STR)
+            self.emit(n.kids[0])
             return
         if n.op == "cast":
             if n.name not in ("DOUBLE", "FLOAT"):
@@ -606,10 +825,9 @@ class _Emitter:
             ta, tb = self.type_of(a), self.type_of(b)
             if "dec" in (ta, tb) and self._emit_dec_cmp(n.name, a, ta, b, tb):
                 return
-            for t in (ta, tb):
-                if t in ("date", "ts"):
-                    raise SqlError("comparisons of date / timestamp columns are not supported by "
-                                   "the engine")
+            if ta in ("date", "ts") or tb in ("date", "ts"):
+                self._emit_temporal_cmp(n.name, a, ta, b, tb)
+                return
             target = _common_cmp_type(ta, tb)
             w.append(_CMP[n.name])
             self.emit(a, target)
@@ -622,7 +840,10 @@ class _Emitter:
             if tx == "dec":
                 self._emit_dec_in(x, items)
                 return
-            if tx in ("date", "ts") or any(t in ("dec", "date", "ts") for t in tis):
+            if tx in ("date", "ts"):
+                self._emit_temporal_in(x, tx, items, tis)
+                return
+            if any(t in ("dec", "date", "ts") for t in tis):
                 raise SqlError("IN over a date / timestamp / decimal value is not supported by the "
                                "engine")
             target = tx
@@ -636,10 +857,11 @@ class _Emitter:
                     raise SqlError("incompatible types in IN list")
             if target == "str" and tx not in ("str", "null") and x.op != "lit":
                 # Spark 2.2 InConversion casts the value to STRING (1 IN ('1', '2') is TRUE,
-                # 1 IN ('01') FALSE); the interpreter has no cast to string outside a regex, and
-                # comparing the number with the strings as they are would make every row FALSE
+                # 1 IN ('01') FALSE); comparing the number with the strings as they are would make
+                # every row FALSE, and the implicit cast is left to be written (CAST AS STRING)
                 raise SqlError(f"a {tx} value IN a list of strings (Spark casts the value to "
-                               f"STRING) is not supported by the engine")
+                               f"STRING) is not supported by the engine as it stands: write "
+                               f"CAST(x AS STRING) IN (...)")
             w += [N.X_IN, len(items)]
             self.emit(x, target if target != tx or tx == "str" else None)
             for i in items:
@@ -659,10 +881,10 @@ class _Emitter:
             return
         if n.op == "like":
             if self.type_of(n.kids[0]) != "str":
-                # Spark casts the operand to string; the interpreter has no such cast outside
-                # the regex op
+                # Spark casts the operand to string; the engine leaves that cast to be written
                 raise SqlError(f"LIKE over a {self.type_of(n.kids[0])} operand (Spark casts it to "
-                               f"STRING) is not supported by the engine")
+                               f"STRING) is not supported by the engine as it stands: write "
+                               f"CAST(x AS STRING) LIKE ...")
             blob = n.value
             w += [N.X_LIKE, len(blob)]
             padded = blob + b"\0" * ((-len(blob)) % 8)
@@ -675,6 +897,11 @@ class _Emitter:
             w += [N.X_ARITH, which, self.result_type(n)]
             for k in n.kids:
                 self.emit_operand(k, what)
+            return
+        if n.op == "func" and n.name in _DATE_FUNCS:
+            w += [N.X_FUNC, _FUNC_CODE[n.name], self.result_type(n), len(n.kids)]
+            for k in n.kids:
+                self.emit(k)
             return
         if n.op == "func":
             rt = self.result_type(n)
@@ -749,7 +976,9 @@ class _Emitter:
 
 _FLIP = {"<": ">", "<=": ">=", ">": "<", ">=": "<="}
 _ARITH = {"+": N.AR_ADD, "-": N.AR_SUB, "*": N.AR_MUL, "/": N.AR_DIV, "%": N.AR_MOD}
-_FUNC_CODE = {"abs": N.FN_ABS, "length": N.FN_LENGTH, "isnan": N.FN_ISNAN}
+_FUNC_CODE = {"abs": N.FN_ABS, "length": N.FN_LENGTH, "isnan": N.FN_ISNAN, "year": N.FN_YEAR,
+              "month": N.FN_MONTH, "dayofmonth": N.FN_DAYOFMONTH, "to_date": N.FN_TO_DATE,
+              "datediff": N.FN_DATEDIFF, "date_add": N.FN_DATE_ADD, "date_sub": N.FN_DATE_SUB}
 
 
 _REGEX_CACHE = {}

@@ -190,8 +190,8 @@ typedef enum dq_xop {
                           decimal column may appear under IS [NOT] NULL, in comparisons / IN with
                           DQ_X_DEC128 items, under DQ_X_CAST_F64 (Decimal.toDouble, correctly
                           rounded) and as a regex operand (BigDecimal.toString text); a date /
-                          timestamp column under IS [NOT] NULL and as a regex operand.  Any other
-                          use is refused by dq_plan_create with DQ_ERR_UNSUPPORTED.            */
+                          timestamp column as DQ_X_TIMESTAMP describes.  Any other use is refused
+                          by dq_plan_create with DQ_ERR_UNSUPPORTED.                           */
   DQ_X_LIKE = 24,      /* [op, nbytes, ceil(n/8) words, x]  x LIKE pattern over a string x (the
                           whole string must match; NULL on a NULL x).  The words pack a pattern
                           program the host compiled (escapes resolved, adjacent % collapsed): a
@@ -207,14 +207,40 @@ typedef enum dq_xop {
                           a DQ_FLOAT32 result is computed in float.  NULL when an operand is
                           NULL, and for / and % when the divisor equals 0 (0.0, -0.0).  % takes
                           the dividend's sign (Java's %, fmod for floats).                      */
-  DQ_X_FUNC = 26       /* [op, which, result_type, n_args, args...]  a dq_func.  DQ_FN_ABS (1
+  DQ_X_FUNC = 26,      /* [op, which, result_type, n_args, args...]  a dq_func.  DQ_FN_ABS (1
                           numeric argument; abs(MIN) wraps), DQ_FN_LENGTH (1 string argument;
                           result_type DQ_INT32: the number of code points), DQ_FN_COALESCE (2-8
                           arguments, all numeric -- converted to result_type -- or all strings,
                           result_type DQ_UTF8: the first non-NULL one), DQ_FN_ISNAN (1 float /
                           double argument; result_type DQ_BOOL; FALSE on NULL).  An expression
                           holding one of these three operators is always evaluated by the
-                          generic interpreter (an expression bitmap), never fused.            */
+                          generic interpreter (an expression bitmap), never fused.
+                          The date functions take date or timestamp arguments (a timestamp is
+                          first cast to date: the floor of micros / 86 400 000 000, UTC) and are
+                          NULL on a NULL argument: DQ_FN_YEAR, DQ_FN_MONTH, DQ_FN_DAYOFMONTH (1
+                          argument; result_type DQ_INT32: the proleptic-Gregorian field),
+                          DQ_FN_TO_DATE (1 argument; result_type DQ_DATE32), DQ_FN_DATEDIFF (end,
+                          start; result_type DQ_INT32: end - start in days), DQ_FN_DATE_ADD and
+                          DQ_FN_DATE_SUB (date, n days -- an integral value; result_type
+                          DQ_DATE32, wrapping at int32 like Spark's Int addition).             */
+  DQ_X_CAST_STR = 27,  /* [op, x]  CAST(x AS STRING), Spark 2.2's text of any value: a string is
+                          itself, true / false, decimal digits, Float.toString / Double.toString
+                          (a DQ_FLOAT32 column or a DQ_X_CAST_F32 result prints as a float),
+                          BigDecimal.toString, yyyy-MM-dd, yyyy-MM-dd HH:mm:ss[.f] in UTC; NULL
+                          on NULL.  The result is a string operand like any other (comparisons,
+                          IN, LIKE, regex, DQ_FN_LENGTH, DQ_FN_COALESCE, DQ_X_CAST_F64).  The
+                          interpreter prints into one of two per-row text slots, which
+                          dq_plan_create assigns: an expression that needs more than two printed
+                          values alive at once is refused with DQ_ERR_UNSUPPORTED.             */
+  DQ_X_DATE = 28,      /* [op, days]    date literal: days since 1970-01-01 (int32 range)        */
+  DQ_X_TIMESTAMP = 29  /* [op, micros]  timestamp literal: microseconds since the epoch, UTC.
+                          A date / timestamp value (column, literal, DQ_FN_TO_DATE / DQ_FN_DATE_ADD
+                          / DQ_FN_DATE_SUB result) may appear under IS [NOT] NULL, as a regex
+                          operand, under DQ_X_CAST_STR, as a date function's argument, and in a
+                          comparison / IN whose other operands are of its own type or NULL (days
+                          and microseconds compare as integers).  Any other use is refused by
+                          dq_plan_create with DQ_ERR_UNSUPPORTED: the host casts one side to
+                          string first, as Spark 2.2's PromoteStrings does.                    */
 } dq_xop;
 
 typedef enum dq_arith_op {
@@ -222,7 +248,10 @@ typedef enum dq_arith_op {
 } dq_arith_op;
 
 typedef enum dq_func {
-  DQ_FN_ABS = 1, DQ_FN_LENGTH = 2, DQ_FN_COALESCE = 3, DQ_FN_ISNAN = 4
+  DQ_FN_ABS = 1, DQ_FN_LENGTH = 2, DQ_FN_COALESCE = 3, DQ_FN_ISNAN = 4,
+  /* date functions */
+  DQ_FN_YEAR = 16, DQ_FN_MONTH = 17, DQ_FN_DAYOFMONTH = 18, DQ_FN_TO_DATE = 19, DQ_FN_DATEDIFF = 20,
+  DQ_FN_DATE_ADD = 21, DQ_FN_DATE_SUB = 22
 } dq_func;
 
 enum { DQ_LIKE_LIT = 1, DQ_LIKE_ANY1 = 2, DQ_LIKE_ANYSEQ = 3, DQ_LIKE_MAX_BYTES = 4096 };
